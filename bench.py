@@ -9,10 +9,14 @@ batch-1 greedy decode. One "step" = every in-flight sequence advances by one tok
           (N micro-steps per step; activations handed on with RCCL send/recv), N tokens per step.
 Per-GPU HBM traffic per step is the same for every N (each rank streams its window N times) -> "weak".
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, config). A plain run only sets up,
+warms up, times --steps steps and prints that line. --dump-outputs DIR also writes the last timed step's output row (what
+pm355_ring_decode_last_output hands a caller: float32 [n_embd], one file per rank) as DIR/last_output[_rank<r>].npy.
+--full adds everything that takes runs of its own, among them:
   roofline     — dominant kernel (Q4_K gate/up mat-vec) timed live with HIP events on its launch stream
   cpu_baseline — the UNMODIFIED reference ggml CPU backend (oracle/_ref) timed on this host's cores on a
                  bounded sample of the same workload (N=1, rank 0 only)
+  prefill / extra configs / plug-in decode / parity check / weight streaming (N=1), single stream + ring prefill (N>1)
 """
 import argparse
 import json
@@ -45,6 +49,9 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip extra_configs / plugin_decode / the llama_decode CPU baseline")
     ap.add_argument("--tmp", default=os.environ.get("TMPDIR", "/tmp"), help="where the synthetic GGUF files of the plug-in legs go")
     ap.add_argument("--section", default="", help="(internal) run ONE extra leg in this process and print its JSON: prefill_qwen | long_context[:model]")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond the headline (roofline probe, prefill, CPU baseline, "
+                                                        "extra configs, plug-in decode, parity check; N>1: single stream, ring prefill)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's output row as DIR/*.npy (float32)")
     return ap.parse_args()
 
 
@@ -875,11 +882,17 @@ def main():
         # same kernels but is not a model)
         lo_ = c_ring.last_output(hp["n_embd"])
         finite = bool(lo_ is not None and torch.isfinite(lo_).all().item())
+        # what the timed loop hands its caller after its last step: this rank's output row (seeded weights and prompt: the same from run to run)
+        if a.dump_outputs:
+            assert lo_ is not None, "no output row to dump (did any timed step run?)"
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            name = "last_output.npy" if world == 1 else f"last_output_rank{rank}.npy"
+            np.save(os.path.join(a.dump_outputs, name), lo_.cpu().numpy().astype(np.float32))
 
         # The reference's own mode next to the aggregate: ONE sequence in flight, every token once round the ring with the other ranks idle
         # (rank 0 blocked in recv until it returns, src/llama.cpp:18509) - what exposes the hop latency. And the pipelined prompt pass.
         single = ring_pf = None
-        if world > 1:
+        if world > 1 and a.full:
             tok1 = torch.tensor([1], dtype=torch.int32, device="cuda") if rank == 0 else None
             for _ in range(3):
                 c_ring.single_token(win, 0, tok1)
@@ -937,7 +950,7 @@ def main():
             if single:
                 result["single_stream"] = single
                 result["ring_prefill"] = ring_pf
-            pr = probe_dominant_kernel(win, hp)
+            pr = probe_dominant_kernel(win, hp) if a.full else None
             if pr:
                 result["roofline"] = {"bound": "hbm", "achieved": round(pr["gbs"], 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                       "frac": round(pr["gbs"] / HBM_PEAK_GBS, 4),
@@ -946,12 +959,12 @@ def main():
                                       "avg_launch_us": round(pr["avg_us"], 2), "launched_as": pr["launch"],
                                       "measured_stream_read_peak": round(pr["stream_read_gbs"], 1) if pr.get("stream_read_gbs") else None,
                                       "frac_of_measured_peak": round(pr["gbs"] / pr["stream_read_gbs"], 4) if pr.get("stream_read_gbs") else None}
-            if world == 1 and a.prefill > 0:
+            if world == 1 and a.full and a.prefill > 0:
                 try:
                     result["prefill"] = probe_prefill(hp, mixture, a.prefill)
                 except Exception as e:
                     result["prefill"] = {"error": str(e)}
-            if world == 1 and not a.no_cpu_baseline:
+            if world == 1 and a.full and not a.no_cpu_baseline:
                 try:
                     cb = cpu_baseline(hp, mixture, a.cpu_seconds)
                 except Exception as e:                       # the baseline is a reported extra, never fatal
@@ -962,7 +975,7 @@ def main():
                     result["cpu_baseline"] = cb
         win.close()
         win = None
-        if rank == 0 and world == 1 and not a.no_extras:
+        if rank == 0 and world == 1 and a.full and not a.no_extras:
             torch.cuda.empty_cache()
             extras = []
             for name in ("llama3-8b", "qwen2.5-72b"):

@@ -359,7 +359,7 @@ def test_bench_two_ranks_on_one_gpu_end_to_end():
     env = dict(os.environ, PM355_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--model", "llama3-8b", "--steps", "4", "--warmup", "2",
-           "--no-extras", "--no-cpu-baseline", "--prefill", "0", "--n-ctx", "2048"]
+           "--full", "--no-extras", "--no-cpu-baseline", "--prefill", "0", "--n-ctx", "2048"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

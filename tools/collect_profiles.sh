@@ -9,9 +9,9 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 # (1) decode: kernel trace of the default bench workload (Llama-3-70B Q4_K_M) -> per-kernel table + one-token timeline
-rm -rf /tmp/prof_dec && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_dec -- python $OLDPWD/bench.py --steps 32 --warmup 4 --no-cpu-baseline --no-extras --prefill 0 > $OUT/${R}_bench_under_profiler.json 2>/dev/null
+rm -rf /tmp/prof_dec && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_dec -- python $OLDPWD/bench.py --full --steps 32 --warmup 4 --no-cpu-baseline --no-extras --prefill 0 > $OUT/${R}_bench_under_profiler.json 2>/dev/null
 f=$(find /tmp/prof_dec -name "*kernel_trace.csv" | head -1)
-{ echo "rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 32 --warmup 4 --no-cpu-baseline --no-extras --prefill 0"; echo "(Llama-3-70B Q4_K_M decode: 52 tokens; tools/prof_summary.py <trace> 53, tools/timeline.py <trace>)"; echo;
+{ echo "rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 32 --warmup 4 --no-cpu-baseline --no-extras --prefill 0"; echo "(Llama-3-70B Q4_K_M decode: 52 tokens; tools/prof_summary.py <trace> 53, tools/timeline.py <trace>)"; echo;
   python $OLDPWD/tools/prof_summary.py $f 53; echo; python $OLDPWD/tools/timeline.py $f 3; } > $OUT/${R}_decode_summary.txt
 cp $(find /tmp/prof_dec -name "*kernel_stats.csv" | head -1) $OUT/${R}_decode_kernel_stats.csv 2>/dev/null
 # (2) HBM traffic of the dominant decode kernel: FETCH_SIZE / WRITE_SIZE, one pass each
