@@ -45,9 +45,6 @@ struct pm355_model {
     uint8_t * aq_k = nullptr, * aq_0 = nullptr;     // quantized activation scratch (Q8_K / Q8_0), sized for max(K)
     int32_t * d_pos = nullptr, * d_tok = nullptr, * d_ctl = nullptr;   // d_pos[n_seq]; d_ctl = {current seq, n_seq}
     int n_seq = 1;
-    bool no_fuse = false;                 // PM355_NO_FUSE=1: node-by-node kernels (debug / A-B)
-    bool no_multi = false;                // PM355_NO_MMQ_MULTI=1
-    bool no_small_cols = false;           // PM355_SMALL_COLS=0
     bool no_small_epi = false;            // PM355_SMALL_ROPE_EPI=0: small batches run rope_kv_store as a launch of its own
     bool no_mmq = false;                  // PM355_NO_MMQ_I8=1: 4..64-token batches on the round-1 paths (mat-vec columns, F16 GEMM from 16 tokens)
     // single-token decode, short contexts, NORM-mode rope: RoPE + F16 KV store happen in the epilogue of the wq | wk | wv launch (per-token cos / sin
@@ -282,13 +279,15 @@ const int MMQ_MIN_TOKENS = 3;                           // (3 columns cost the m
 // moves the crossover (the F16 path is the prompt's parity tier: activations not re-quantized)
 const int MMQ_MAX_TOKENS = [] { const char * e = getenv("PM355_MMQ_MAX_TOKENS"); const int v = e ? atoi(e) : 0; return v >= 16 && v <= 64 ? v : 32; }();
 // small batches from this size on attend through the prompt path's matrix-core kernel (attn_prefill.hip: one workgroup per head, the same rounding points);
-// below it one workgroup per (head, token) (attn_cached.hip). 70B layer at 16 / 24 / 32 tokens: 190.1 / 219.1 / 229.9 -> 188.9 / 214.0 / 217.0 us
-const int SMALL_ATTN_MFMA_MIN = [] { const char * e = getenv("PM355_SMALL_ATTN_MFMA_MIN"); return e ? atoi(e) : 16; }();
+// below it one workgroup per (head, token) (attn_cached.hip). 70B layer at 16 / 24 / 32 tokens: 190.1 / 219.1 / 229.9 -> 188.9 / 214.0 / 217.0 us.
+// PM355_SMALL_ATTN_MFMA_MIN >= 2 moves it
+const int SMALL_ATTN_MFMA_MIN = [] { const char * e = getenv("PM355_SMALL_ATTN_MFMA_MIN"); const int v = e ? atoi(e) : 0; return v >= 2 ? v : 16; }();
 const int MMQ_MULTI_MIN_TOKENS = 2;       // the fused wq | wk | wv and ffn_gate | ffn_up launches already win at 2 tokens (3 / 4 mat-vec launches otherwise)
+const int VEC_MAX_TOKENS = 15;            // a layer the small-batch mat-mul does not serve: largest batch on the multi-column mat-vec, beyond it the F16 GEMMs
 // the table output of the Q8_K quantizers, when this batch size takes the small-batch mat-mul (mmq_i8.hip)
 pm_q8k_tables mmq_tables(const pm355_model * m, int K, int T, hipStream_t st) {
     pm_q8k_tables tb;
-    const bool on = T >= (m->no_multi ? MMQ_MIN_TOKENS : MMQ_MULTI_MIN_TOKENS) && T <= MMQ_MAX_TOKENS && !m->no_mmq;
+    const bool on = T >= MMQ_MULTI_MIN_TOKENS && T <= MMQ_MAX_TOKENS && !m->no_mmq;
     if (on && pm_mmq_i8_tables(K, st, &tb) != 0) tb = pm_q8k_tables();
     return on ? tb : pm_q8k_tables();
 }
@@ -361,14 +360,9 @@ int run_head(pm355_model * m, const float * x_row, float * d_logits, int32_t * d
     if (!m->output.d || !m->out_norm.d) return seterr(m, PM355_E_UNSUPPORTED, "head: output / output_norm missing");
     const Tensor * ow[1] = {&m->output};
     float * lg = d_logits ? d_logits : m->logits;
-    if (!m->no_fuse) {
-        float * y[1] = {lg};
-        if (gemv_f32(m, ow, nullptr, y, nullptr, nullptr, 1, x_row, (const float *) m->out_norm.d, st, nullptr, nullptr, nullptr, ss_in, n_ss_in))
-            return seterr(m, PM355_E_UNSUPPORTED, "head: fused lm_head gemv");
-    } else {
-        ActQ a = norm_quantize_for(m, x_row, (const float *) m->out_norm.d, m->hp.n_embd, 1, ow, 1, st);
-        if (gemv(m->output, nullptr, a, 1, lg, nullptr, nullptr, st)) return seterr(m, PM355_E_UNSUPPORTED, "head: lm_head gemv");
-    }
+    float * y[1] = {lg};
+    if (gemv_f32(m, ow, nullptr, y, nullptr, nullptr, 1, x_row, (const float *) m->out_norm.d, st, nullptr, nullptr, nullptr, ss_in, n_ss_in))
+        return seterr(m, PM355_E_UNSUPPORTED, "head: fused lm_head gemv");
     if (d_argmax) pm_launch_argmax(lg, m->hp.n_vocab, d_argmax, nullptr, st);
     return 0;
 }
@@ -460,7 +454,7 @@ pm355_model::EnginePlan * engine_plan_for(pm355_model * m, const float * cur, fl
 pm355_model::EnginePlan * engine_plan_for(pm355_model *, const float *, float *, bool = true) { return nullptr; }      // (experiments library only)
 #endif
 bool engine_eligible(const pm355_model * m) {
-    return m->use_engine && !m->no_fuse && !m->long_ctx && !m->n_slots && m->ss && m->qkv_epi && m->rope_tab && (m->rope.mode == 0 || m->rope.mode == 2) && m->hi > m->lo;
+    return m->use_engine && !m->long_ctx && !m->n_slots && m->ss && m->qkv_epi && m->rope_tab && (m->rope.mode == 0 || m->rope.mode == 2) && m->hi > m->lo;
 }
 
 // which single-token attention path the current sequence takes: 0 = one workgroup per head; else the cells the long-context grid is
@@ -575,14 +569,247 @@ int run_layers_fused(pm355_model * m, const float * cur, float * d_x_out, const 
     return 0;
 }
 
+// ---- multi-token windows: every layer takes one of three paths, chosen per layer (Q4_K_M mixes types across layers) --------------------------
+// each path: cur [T][E] -> x_mid = cur + attention(cur) -> x_next = x_mid + ffn(x_mid); returns 0 or the seterr code
+enum class LayerPath { prompt_i8, prompt_f16, small };
+
+LayerPath layer_path(const pm355_model * m, const Layer & L, int T) {
+    // batches up to MMQ_MAX_TOKENS take the small-batch path unless its per-token attention kernel cannot hold n_ctx scores in LDS
+    const bool small_attn_ok = (size_t) (m->hp.head_dim + m->hp.n_ctx) * 4 <= 150 * 1024;
+    bool small_ok = !m->no_mmq && small_attn_ok;              // ... and unless one of the layer's large matrices has a type neither small-batch path serves
+    for (int k : {PM355_T_WQ, PM355_T_WO, PM355_T_FFN_GATE, PM355_T_FFN_UP, PM355_T_FFN_DOWN}) {
+        // Q4_K / Q5_K / Q6_K and (round 4) Q8_0 - Qwen2.5-72B's ffn_down: 29568 % 256 != 0, src/llama.cpp:19547 - on the integer matrix cores
+        // (mmq_i8.hip; Q8_0 with Q8_0 activations = ggml_vec_dot_q8_0_q8_0's arithmetic); a Q8_0 shape it does not serve falls back to the multi-column mat-vec
+        const bool served = pm_mmq_i8_check(L.t[k].type, (int) L.t[k].K, (int) L.t[k].N, std::min(T, MMQ_MAX_TOKENS)) == 0;
+        small_ok = small_ok && (served || L.t[k].type == PM_Q8_0);
+    }
+    // prompts: every large matrix the integer kernel serves (Q4_K / Q6_K, K % 1024 == 0) runs on Q8_K activations with the CPU reference's
+    // arithmetic; wv alone may stay on the F16 GEMM (Llama-3-70B Q4_K_M: Q5_K in half the layers, src/llama.cpp:19360-19373)
+    bool big_ok = T > MMQ_MAX_TOKENS && !m->no_big && m->tab_big && m->h2;
+    for (int k : {PM355_T_WQ, PM355_T_WK, PM355_T_WO, PM355_T_FFN_GATE, PM355_T_FFN_UP, PM355_T_FFN_DOWN})
+        big_ok = big_ok && pm_mmq_big_check(L.t[k].type, (int) L.t[k].K, (int) L.t[k].N, T) == 0;
+    if (big_ok) return LayerPath::prompt_i8;
+    return T > (small_ok ? MMQ_MAX_TOKENS : VEC_MAX_TOKENS) ? LayerPath::prompt_f16 : LayerPath::small;
+}
+// prompts on the integer matrix cores over Q8_K activations (PM355_PROMPT_I8=1, mmq_big.hip)
+int layer_prompt_i8(pm355_model * m, const Layer & L, int T, const float * cur, float * x_mid, float * x_next, hipStream_t st) {
+    const pm355_hparams & hp = m->hp;
+    const int E = hp.n_embd, H = hp.n_head, Hkv = hp.n_head_kv, dh = hp.head_dim, F = hp.n_ff;
+    const float kq_scale = 1.0f / sqrtf((float) dh);
+    auto TB = [&](int K) { pm_q8k_tables tb; tb.base = m->tab_big; tb.tab_bytes = (size_t) (K / 256) * (1024 + 128); tb.nsb = K / 256; return tb; };
+    auto GI = [&](const Tensor & w, float * y, const float * bias, const float * resid, hipStream_t s2 = nullptr) {
+        return pm_launch_mmq_big(w.type, w.d, m->aq_k, m->tab_big, y, (int) w.K, (int) w.N, T, bias, resid, s2 ? s2 : st);
+    };
+    const Tensor & wv = L.t[PM355_T_WV];
+    const bool wv8 = pm_mmq_big_check(wv.type, (int) wv.K, (int) wv.N, T) == 0;
+    pm_launch_rmsnorm_q8k(cur, (const float *) L.t[PM355_T_ATTN_NORM].d, nullptr, m->aq_k, E, T, hp.rms_eps, st, wv8 ? nullptr : m->xn, TB(E));
+    int rc = GI(L.t[PM355_T_WQ], m->q, (const float *) L.t[PM355_T_BQ].d, nullptr);
+    if (!m->side) {
+        if (hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&m->side_a, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&m->side_b, hipEventDisableTiming) != hipSuccess) return seterr(m, PM355_E_HIP, "prefill: side stream");
+    }
+    (void) hipEventRecord(m->side_a, st);
+    (void) hipStreamWaitEvent(m->side, m->side_a, 0);
+    rc |= GI(L.t[PM355_T_WK], m->k, (const float *) L.t[PM355_T_BK].d, nullptr);
+    rc |= wv8 ? GI(wv, m->v, (const float *) L.t[PM355_T_BV].d, nullptr, m->side)
+              : pm_launch_gemm_q_h(wv.type, wv.d, nullptr, m->xn, m->v, nullptr, (int) wv.K, (int) wv.N, T, (const float *) L.t[PM355_T_BV].d, nullptr, nullptr, 0, m->side);
+    (void) hipEventRecord(m->side_b, m->side);
+    (void) hipStreamWaitEvent(st, m->side_b, 0);
+    if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: qkv mat-mul (integer matrix cores)");
+    const long kvs = (long) hp.n_ctx * Hkv * dh;
+    pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kvs,
+                            (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st);
+    if (pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st) &&
+        pm_launch_attn_decode(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st))
+        return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
+    pm_launch_quantize_q8k(m->att, m->aq_k, H * dh, T, st, TB(H * dh));
+    if (GI(L.t[PM355_T_WO], x_mid, nullptr, cur)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: wo mat-mul");
+    pm_launch_rmsnorm_q8k(x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, nullptr, m->aq_k, E, T, hp.rms_eps, st, nullptr, TB(E));
+    if (GI(L.t[PM355_T_FFN_GATE], m->h, nullptr, nullptr) || GI(L.t[PM355_T_FFN_UP], m->h2, nullptr, nullptr))
+        return seterr(m, PM355_E_UNSUPPORTED, "prefill: gate/up mat-mul");
+    pm_launch_silu_mul_q8k(m->h, m->h2, m->aq_k, F, T, st, TB(F));                   // silu(gate) * up straight into ffn_down's Q8_K rows
+    return GI(L.t[PM355_T_FFN_DOWN], x_next, nullptr, x_mid) ? seterr(m, PM355_E_UNSUPPORTED, "prefill: down mat-mul") : 0;
+}
+// prompts: batched GEMMs on the MFMA matrix cores (mmq_pf.hip / mmq.hip), f32 activations
+// F16 plumbing: the producers of GEMM activations write them as F16 (the rounding the GEMM's own conversion pass would apply) into
+// the engine's scratch - xn / att in place of their f32 forms, h = silu(gate) * up into h2: no conversion launches, half the bytes
+int layer_prompt_f16(pm355_model * m, const Layer & L, int T, const float * cur, float * x_mid, float * x_next, hipStream_t st) {
+    const pm355_hparams & hp = m->hp;
+    const int E = hp.n_embd, H = hp.n_head, Hkv = hp.n_head_kv, dh = hp.head_dim;
+    const float kq_scale = 1.0f / sqrtf((float) dh);
+    auto G = [&](const Tensor & w, const void * xh, float * y, void * yh, const float * bias, const float * resid,
+                 const float * silu_gate = nullptr, hipStream_t s2 = nullptr) {
+        return pm_launch_gemm_q_h(w.type, w.d, nullptr, xh, y, yh, (int) w.K, (int) w.N, T, bias, resid, silu_gate, 0, s2 ? s2 : st);
+    };
+    pm_launch_rmsnorm_q8k(cur, (const float *) L.t[PM355_T_ATTN_NORM].d, nullptr, nullptr, E, T, hp.rms_eps, st, m->xn);
+    // wq | wk | wv: ONE launch over the shared activations, each matrix with its own quant type (mmq_pf.hip jobs; wk / wv alone - N = n_head_kv * head_dim -
+    // filled a fraction of the chip: 212 TFLOP/s as their own launches)
+    int rc;
+    {
+        const Tensor & wq = L.t[PM355_T_WQ], & wk = L.t[PM355_T_WK], & wv = L.t[PM355_T_WV];
+        const pm_gemm_pf_job qkvj[3] = {
+            {wq.type, (int) wq.N, wq.d, m->q, nullptr, (const float *) L.t[PM355_T_BQ].d, nullptr, nullptr, 0},
+            {wk.type, (int) wk.N, wk.d, m->k, nullptr, (const float *) L.t[PM355_T_BK].d, nullptr, nullptr, 0},
+            {wv.type, (int) wv.N, wv.d, m->v, nullptr, (const float *) L.t[PM355_T_BV].d, nullptr, nullptr, 0}};
+        rc = pm_launch_gemm_q_multi(qkvj, 3, nullptr, m->xn, E, T, st);
+    }
+    if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: qkv gemm");
+    const long kvs = (long) hp.n_ctx * Hkv * dh;
+    pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kvs,
+                            (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st);
+    bool att_h = true;
+    if (pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, nullptr, T, H, Hkv, dh, hp.n_ctx, kq_scale, st, nullptr, 0, 0, 0, 0, m->att)) {
+        att_h = false;
+        if (pm_launch_attn_decode(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st))
+            return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
+    }
+    const Tensor & wo = L.t[PM355_T_WO];
+    if (att_h ? G(wo, m->att, x_mid, nullptr, nullptr, cur)
+              : pm_launch_gemm_q_ex(wo.type, wo.d, m->att, x_mid, (int) wo.K, (int) wo.N, T, nullptr, cur, nullptr, 0, st))
+        return seterr(m, PM355_E_UNSUPPORTED, "prefill: wo gemm");
+    pm_launch_rmsnorm_q8k(x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, nullptr, nullptr, E, T, hp.rms_eps, st, m->xn);
+    {
+        // ffn_gate | ffn_up as ONE launch of pair tiles: h2 = F16(silu(gate) * up) comes out of the up waves' epilogue, the gate result crosses over inside
+        // the workgroup and never reaches HBM (two launches: gate as f32, read back by ffn_up's epilogue - 2 x T x n_ff x 4 bytes per layer)
+        const Tensor & wg = L.t[PM355_T_FFN_GATE], & wu = L.t[PM355_T_FFN_UP];
+        const pm_gemm_pf_job gu[2] = {{wg.type, (int) wg.N, wg.d, nullptr, nullptr, nullptr, nullptr, nullptr, 0},
+                                      {wu.type, (int) wu.N, wu.d, nullptr, m->h2, nullptr, nullptr, nullptr, 0}};
+        if (wg.type == wu.type && wg.N == wu.N && pm_gemm_pf_check(wg.type, E, (int) wg.N, T) == 0 && pm_gemm_pf_enabled())
+            rc = pm_launch_gemm_pf_ex(gu, 2, m->xn, E, T, 1, st);
+        else {
+            rc = G(wg, m->xn, m->h, nullptr, nullptr, nullptr);
+            rc |= G(wu, m->xn, nullptr, m->h2, nullptr, nullptr, m->h);                          // h2 = F16(silu(gate) * up), in the epilogue
+        }
+    }
+    if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: gate/up gemm");
+    return G(L.t[PM355_T_FFN_DOWN], m->h2, x_next, nullptr, nullptr, x_mid) ? seterr(m, PM355_E_UNSUPPORTED, "prefill: down gemm") : 0;
+}
+// small batches (2..32 tokens) with NORM rope: RoPE + KV store ride in the epilogue of the wq | wk | wv small-batch launch; run_window writes
+// the tokens' cos / sin tables once for all layers. PM355_SMALL_ROPE_EPI=0: the separate rope_kv_store launch
+bool small_rope_epi(const pm355_model * m, int T) {
+    return T >= MMQ_MULTI_MIN_TOKENS && T <= 32 && T <= MMQ_MAX_TOKENS && !m->no_mmq && !m->no_small_epi && m->qkv_epi && m->rope_tab &&
+           m->rope.mode == 0 && m->hi > m->lo;
+}
+// matrices of one type that share the activations go out as ONE small-batch launch per 32 tokens: wq | wk (| wv), ffn_gate | ffn_up
+int mmq_multi(const Tensor * const * ws, float * const * ys, const float * const * bs, int n, const ActQ & a, int T, hipStream_t st,
+              const pm_qkv_epi * epi = nullptr) {
+    const void * W[3]; int N[3];
+    for (int j = 0; j < n; ++j) { W[j] = ws[j]->d; N[j] = (int) ws[j]->N; }
+    return pm_launch_mmq_i8_multi(ws[0]->type, n, W, N, ys, bs, a.k, (int) ws[0]->K, T, a.tab ? 1 : 0, st, epi);
+}
+// wq | wk | wv of a small batch (small: the small-batch mat-mul takes it). Each fused launch is tried first with RoPE + KV store in its
+// epilogue (rope_done), then without: all three of one type; else wv of another K-quant type (Q6_K / Q5_K in the Q4_K_M files) in the same
+// grid, its own workgroups (mmq_i8_dual_kernel); else wq | wk and wv alone. Otherwise one mat-mul per matrix
+int small_qkv(pm355_model * m, const Layer & L, const ActQ & a, int T, bool small, bool & rope_done, hipStream_t st) {
+    const pm355_hparams & hp = m->hp;
+    const Tensor * ws[3] = {&L.t[PM355_T_WQ], &L.t[PM355_T_WK], &L.t[PM355_T_WV]};
+    float * ys[3] = {m->q, m->k, m->v};
+    const float * bs[3] = {(const float *) L.t[PM355_T_BQ].d, (const float *) L.t[PM355_T_BK].d, (const float *) L.t[PM355_T_BV].d};
+    const Tensor & wq = *ws[0], & wk = *ws[1], & wv = *ws[2];
+    const pm_qkv_epi qe = {m->rope_tab, m->d_pos, m->d_ctl, nullptr, (long) hp.n_ctx * hp.n_head_kv * hp.head_dim, L.kc, L.vc, hp.n_head_kv, hp.head_dim,
+                           hp.n_ctx, m->rope.n_dims, 0, 0};
+    const pm_qkv_epi * epi = small_rope_epi(m, T) ? &qe : nullptr;
+    auto fused = [&](auto && launch) {
+        if (epi && launch(epi) == 0) return rope_done = true;
+        return launch(nullptr) == 0;
+    };
+    bool prepped = false;
+    if (small && wq.type == wk.type) {
+        if (wv.type == wq.type) {
+            if (fused([&](const pm_qkv_epi * e) { return mmq_multi(ws, ys, bs, 3, a, T, st, e); })) return 0;
+        } else {
+            const void * W[2] = {wq.d, wk.d}; const int N[2] = {(int) wq.N, (int) wk.N};
+            if (wv.K == wq.K && fused([&](const pm_qkv_epi * e) {
+                    return pm_launch_mmq_i8_dual(wq.type, 2, W, N, ys, bs, wv.type, wv.d, (int) wv.N, m->v, bs[2], a.k, (int) wq.K, T, a.tab ? 1 : 0, st, e); }))
+                return 0;
+            if (mmq_multi(ws, ys, bs, 2, a, T, st) == 0) { prepped = true; return matmul_small(m, wv, a, T, m->v, bs[2], nullptr, prepped, st); }
+        }
+    }
+    int rc = 0;
+    for (int j = 0; j < 3; ++j) rc |= matmul_small(m, *ws[j], a, T, ys[j], bs[j], nullptr, prepped, st);
+    return rc;
+}
+// RoPE + KV store (unless the wq | wk | wv epilogue did them), attention, wo + residual -> x_mid
+int small_attention(pm355_model * m, const Layer & L, int T, bool rope_done, const float * cur, float * x_mid, hipStream_t st) {
+    const pm355_hparams & hp = m->hp;
+    const int H = hp.n_head, Hkv = hp.n_head_kv, dh = hp.head_dim;
+    const float kq_scale = 1.0f / sqrtf((float) dh);
+    const long kv_stride = (long) hp.n_ctx * Hkv * dh;
+    // q rotated AND rounded to F16, every token's K row / V column stored: the attention of a small batch then is the single-token kernel over
+    // cached cells, one workgroup per (head, token) (attn_cached.hip: one barrier up to 64 cells; 11 -> ~4 us per layer at 2..8 tokens)
+    if (!rope_done)
+        pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride,
+                                (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st, 1);
+    // (a shape attn_cached refuses - head_dim other than 64 / 128 / 256, scores beyond 150 KiB of LDS - falls back to attn_decode, which rounds q to
+    //  F16 itself: the pre-rounded rows give it the same bits as raw ones, tests/test_gpu_ops.py::test_small_batch_attention_fallback_...)
+    // (from SMALL_ATTN_MFMA_MIN tokens on: the prompt path's matrix-core kernel - 12 us per layer at 32 tokens against 26 for 2048 small workgroups)
+    if (!(T >= SMALL_ATTN_MFMA_MIN && pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st) == 0) &&
+        pm_launch_attn_cached(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, H, Hkv, dh, hp.n_ctx, kq_scale, st, nullptr, nullptr, 0, 0, 0, T) &&
+        pm_launch_attn_decode(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st))
+        return seterr(m, PM355_E_RANGE, "decode: n_ctx too large for the decode-attention kernel");
+    const Tensor * wo[1] = {&L.t[PM355_T_WO]};
+    const ActQ a = quantize_for(m, m->att, H * dh, T, wo, 1, st);
+    bool prepped = false;
+    return matmul_small(m, L.t[PM355_T_WO], a, T, x_mid, nullptr, cur, prepped, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: wo gemv") : 0;
+}
+// ffn_norm, ffn_gate | ffn_up, silu * mul, ffn_down + residual -> x_next
+int small_ffn(pm355_model * m, const Layer & L, int T, bool small, const float * x_mid, float * x_next, hipStream_t st) {
+    const int E = m->hp.n_embd, F = m->hp.n_ff;
+    const Tensor & wg = L.t[PM355_T_FFN_GATE], & wu = L.t[PM355_T_FFN_UP], & wd = L.t[PM355_T_FFN_DOWN];
+    const Tensor * gu[2] = {&wg, &wu};
+    ActQ a = norm_quantize_for(m, x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, E, T, gu, 2, st);
+    if (wg.type != wu.type) return seterr(m, PM355_E_UNSUPPORTED, "decode: ffn_gate and ffn_up of different types");
+    bool prepped = false, gu_done = false;
+    // 2 tokens: the pair mat-vec with two column slots - one pass over both matrices, silu(gate) * up in its epilogue (~50 us against 60 for the
+    // two-matrix launch of the matrix-core kernel + the product launch)
+    const bool pair_cols = T == 2 && (wg.type == PM_Q4_K || wg.type == PM_Q6_K);
+    if (!pair_cols && small && m->h2 && pm_mmq_i8_check(wg.type, (int) wg.K, (int) wg.N, T) == 0) {
+        // gate and up: one weight pass each for all tokens, then silu(gate) * up (the pair mat-vec would take one launch per token)
+        float * ys[2] = {m->h, m->h2}; const float * bs[2] = {nullptr, nullptr};
+        if (mmq_multi(gu, ys, bs, 2, a, T, st) == 0) gu_done = true;
+        else if (T >= MMQ_MIN_TOKENS) {
+            if (matmul_small(m, wg, a, T, m->h, nullptr, nullptr, prepped, st) || matmul_small(m, wu, a, T, m->h2, nullptr, nullptr, prepped, st))
+                return seterr(m, PM355_E_UNSUPPORTED, "decode: gate/up small-batch mat-mul");
+            gu_done = true;
+        }
+    }
+    if (!gu_done && gemv(wg, &wu, a, T, m->h, nullptr, nullptr, st)) return seterr(m, PM355_E_UNSUPPORTED, "decode: gate/up gemv");
+    if (gu_done && wd.type != PM_Q8_0) {
+        // silu(gate) * up goes straight into the Q8_K rows (and activation tables) ffn_down reads: no f32 product, one launch less
+        const pm_q8k_tables tb = mmq_tables(m, F, T, st);
+        pm_launch_silu_mul_q8k(m->h, m->h2, m->aq_k, F, T, st, tb);
+        a = ActQ(); a.k = m->aq_k; a.tab = tb.base != nullptr;
+    } else {
+        // Q8_0 ffn_down (n_ff no multiple of 256) on the small-batch mat-mul: silu(gate) * up quantized straight into its activation tables - one launch
+        // instead of silu_mul, quantize_q80 and the mat-mul's table prologue
+        void * tab = nullptr; size_t qb = 0, db = 0;
+        if (gu_done && T >= MMQ_MIN_TOKENS && pm_mmq_i8_check(wd.type, (int) wd.K, (int) wd.N, T) == 0 && pm_mmq_i8_q80_tables((int) wd.K, st, &tab, &qb, &db) == 0) {
+            pm_launch_silu_mul_q80_tab(m->h, m->h2, tab, qb, db, F, T, st);
+            return pm_launch_mmq_i8(wd.type, wd.d, nullptr, nullptr, x_next, (int) wd.K, (int) wd.N, T, nullptr, x_mid, 1, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: down mat-mul") : 0;
+        }
+        if (gu_done) pm_launch_silu_mul(m->h, m->h2, m->h, (long) T * F, st);
+        const Tensor * dn[1] = {&wd};
+        a = quantize_for(m, m->h, F, T, dn, 1, st);
+    }
+    prepped = false;
+    return matmul_small(m, wd, a, T, x_next, nullptr, x_mid, prepped, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: down gemv") : 0;
+}
+// small batches, T = 2 .. MMQ_MAX_TOKENS: the small-batch mat-mul (mmq_i8.hip) where it serves the types, else the multi-column mat-vec (mmvq_cols.hip)
+int layer_small(pm355_model * m, const Layer & L, int T, const float * cur, float * x_mid, float * x_next, hipStream_t st) {
+    // attn_norm (+weight), quantized for q/k/v in the same pass when only Q8_K is needed
+    const Tensor * qkv[3] = {&L.t[PM355_T_WQ], &L.t[PM355_T_WK], &L.t[PM355_T_WV]};
+    const ActQ a = norm_quantize_for(m, cur, (const float *) L.t[PM355_T_ATTN_NORM].d, m->hp.n_embd, T, qkv, 3, st);
+    const bool small = !m->no_mmq && a.k != nullptr;        // (single launches: from MMQ_MIN_TOKENS, in matmul_small)
+    bool rope_done = false;
+    if (int rc = small_qkv(m, L, a, T, small, rope_done, st)) return seterr(m, rc, "decode: qkv gemv");
+    if (int rc = small_attention(m, L, T, rope_done, cur, x_mid, st)) return rc;
+    return small_ffn(m, L, T, small, x_mid, x_next, st);
+}
 // x_in -> x_out for layers [lo, hi); positions from device memory d_pos (pos of token 0)
 int run_window(pm355_model * m, const int32_t * d_tokens, const float * d_x_in, int T, float * d_x_out,
                float * d_logits, int32_t * d_argmax, hipStream_t st) {
     (void) hipGetLastError();
-    const pm355_hparams & hp = m->hp;
-    const int E = hp.n_embd, H = hp.n_head, Hkv = hp.n_head_kv, dh = hp.head_dim, F = hp.n_ff;
-    const int Eq = H * dh;
-    const float kq_scale = 1.0f / sqrtf((float) dh);
+    const int E = m->hp.n_embd;
     const float * cur = d_x_in;
     if (d_tokens) {
         if (!(m->flags & PM355_HAS_EMBD) || !m->tok_embd.d) return seterr(m, PM355_E_UNSUPPORTED, "decode: tokens given but window has no tok_embd");
@@ -590,14 +817,10 @@ int run_window(pm355_model * m, const int32_t * d_tokens, const float * d_x_in, 
         cur = m->x;
     }
     if (!cur) return seterr(m, PM355_E_SHAPE, "decode: neither tokens nor x_in");
-    float * bufs[2] = {m->x, m->x1};
     int n_ss_head = 0; const double * ss_head = m->ss ? m->ss + 256 : nullptr;   // partials of the output row's sum of squares left by the last ffn_down (single-token path)
-    // small batches (2..32 tokens) with NORM rope: RoPE + KV store ride in the epilogue of the wq | wk | wv small-batch launch; the tokens' cos / sin tables
-    // are written here, once for all layers
-    const bool small_epi = T >= MMQ_MULTI_MIN_TOKENS && T <= 32 && T <= MMQ_MAX_TOKENS && !m->no_fuse && !m->no_mmq && !m->no_multi && !m->no_small_epi && m->qkv_epi && m->rope_tab &&
-                           m->rope.mode == 0 && m->hi > m->lo;
-    if (small_epi) pm_launch_rope_table(m->rope, m->d_pos, m->d_ctl, (const float *) m->rope_freqs.d, m->rope_tab, st, T);
-    if (T == 1 && !m->no_fuse) {
+    if (small_rope_epi(m, T)) pm_launch_rope_table(m->rope, m->d_pos, m->d_ctl, (const float *) m->rope_freqs.d, m->rope_tab, st, T);
+    float * bufs[2] = {m->x, m->x1};
+    if (T == 1) {
         m->flash_cells = attn_regime(m); m->long_ctx = m->flash_cells != 0;
         // ---- single token: every activation transform is fused into a mat-vec prologue / epilogue, 5 launches per layer
         const float * end = nullptr;
@@ -622,237 +845,15 @@ int run_window(pm355_model * m, const int32_t * d_tokens, const float * d_x_in, 
         cur = end;
     } else
     for (int il = m->lo; il < m->hi; ++il) {
-        Layer Lv = layer_acquire(m, il, st); Layer & L = Lv;
-        const Tensor * qkv[3] = {&L.t[PM355_T_WQ], &L.t[PM355_T_WK], &L.t[PM355_T_WV]};
-        // batches up to MMQ_MAX_TOKENS take the small-batch path below unless its per-token attention kernel cannot hold n_ctx scores in LDS
-        const bool small_attn_ok = (size_t) (dh + hp.n_ctx) * 4 <= 150 * 1024;
-        bool small_ok = !m->no_mmq && small_attn_ok;              // ... and unless one of the layer's large matrices has a type neither small-batch path serves
-        for (int k : {PM355_T_WQ, PM355_T_WO, PM355_T_FFN_GATE, PM355_T_FFN_UP, PM355_T_FFN_DOWN}) {
-            // Q4_K / Q5_K / Q6_K and (round 4) Q8_0 - Qwen2.5-72B's ffn_down: 29568 % 256 != 0, src/llama.cpp:19547 - on the integer matrix cores
-            // (mmq_i8.hip; Q8_0 with Q8_0 activations = ggml_vec_dot_q8_0_q8_0's arithmetic); a Q8_0 shape it does not serve falls back to the multi-column mat-vec
-            const bool served = pm_mmq_i8_check(L.t[k].type, (int) L.t[k].K, (int) L.t[k].N, T < 1 ? 1 : (T > MMQ_MAX_TOKENS ? MMQ_MAX_TOKENS : T)) == 0;
-            small_ok = small_ok && (served || L.t[k].type == PM_Q8_0);
-        }
-        // prompts: every large matrix the integer kernel serves (Q4_K / Q6_K, K % 1024 == 0) runs on Q8_K activations with the CPU reference's
-        // arithmetic; wv alone may stay on the F16 GEMM (Llama-3-70B Q4_K_M: Q5_K in half the layers, src/llama.cpp:19360-19373)
-        bool big_ok = T > MMQ_MAX_TOKENS && !m->no_fuse && !m->no_big && m->tab_big && m->h2;
-        for (int k : {PM355_T_WQ, PM355_T_WK, PM355_T_WO, PM355_T_FFN_GATE, PM355_T_FFN_UP, PM355_T_FFN_DOWN})
-            big_ok = big_ok && pm_mmq_big_check(L.t[k].type, (int) L.t[k].K, (int) L.t[k].N, T) == 0;
-        if (big_ok) {
-            auto TB = [&](int K) { pm_q8k_tables tb; tb.base = m->tab_big; tb.tab_bytes = (size_t) (K / 256) * (1024 + 128); tb.nsb = K / 256; return tb; };
-            auto GI = [&](const Tensor & w, float * y, const float * bias, const float * resid, hipStream_t s2 = nullptr) {
-                return pm_launch_mmq_big(w.type, w.d, m->aq_k, m->tab_big, y, (int) w.K, (int) w.N, T, bias, resid, s2 ? s2 : st);
-            };
-            const Tensor & wv = L.t[PM355_T_WV];
-            const bool wv8 = pm_mmq_big_check(wv.type, (int) wv.K, (int) wv.N, T) == 0;
-            pm_launch_rmsnorm_q8k(cur, (const float *) L.t[PM355_T_ATTN_NORM].d, nullptr, m->aq_k, E, T, hp.rms_eps, st, wv8 ? nullptr : m->xn, TB(E));
-            int rc = GI(L.t[PM355_T_WQ], m->q, (const float *) L.t[PM355_T_BQ].d, nullptr);
-            if (!m->side) {
-                if (hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&m->side_a, hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&m->side_b, hipEventDisableTiming) != hipSuccess) return seterr(m, PM355_E_HIP, "prefill: side stream");
-            }
-            (void) hipEventRecord(m->side_a, st);
-            (void) hipStreamWaitEvent(m->side, m->side_a, 0);
-            rc |= GI(L.t[PM355_T_WK], m->k, (const float *) L.t[PM355_T_BK].d, nullptr);
-            rc |= wv8 ? GI(wv, m->v, (const float *) L.t[PM355_T_BV].d, nullptr, m->side)
-                      : pm_launch_gemm_q_h(wv.type, wv.d, nullptr, m->xn, m->v, nullptr, (int) wv.K, (int) wv.N, T, (const float *) L.t[PM355_T_BV].d, nullptr, nullptr, 0, m->side);
-            (void) hipEventRecord(m->side_b, m->side);
-            (void) hipStreamWaitEvent(st, m->side_b, 0);
-            if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: qkv mat-mul (integer matrix cores)");
-            const long kvs = (long) hp.n_ctx * Hkv * dh;
-            pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kvs,
-                                    (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st);
-            if (pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st) &&
-                pm_launch_attn_decode(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st))
-                return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
-            pm_launch_quantize_q8k(m->att, m->aq_k, Eq, T, st, TB(Eq));
-            float * x_mid = (cur == bufs[0]) ? bufs[1] : bufs[0];
-            if (GI(L.t[PM355_T_WO], x_mid, nullptr, cur)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: wo mat-mul");
-            pm_launch_rmsnorm_q8k(x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, nullptr, m->aq_k, E, T, hp.rms_eps, st, nullptr, TB(E));
-            if (GI(L.t[PM355_T_FFN_GATE], m->h, nullptr, nullptr) || GI(L.t[PM355_T_FFN_UP], m->h2, nullptr, nullptr))
-                return seterr(m, PM355_E_UNSUPPORTED, "prefill: gate/up mat-mul");
-            pm_launch_silu_mul_q8k(m->h, m->h2, m->aq_k, F, T, st, TB(F));                   // silu(gate) * up straight into ffn_down's Q8_K rows
-            float * x_next = (il == m->hi - 1 && d_x_out) ? d_x_out : ((x_mid == bufs[0]) ? bufs[1] : bufs[0]);
-            if (GI(L.t[PM355_T_FFN_DOWN], x_next, nullptr, x_mid)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: down mat-mul");
-            layer_release(m, il, st);
-            cur = x_next;
-            continue;
-        }
-        if (T > (small_ok ? MMQ_MAX_TOKENS : 15) && !m->no_fuse) {
-            // ---- prefill: batched GEMMs on the MFMA matrix cores (mmq.hip), f32 activations
-            // F16 plumbing: the producers of GEMM activations write them as F16 (the rounding the GEMM's own conversion pass would apply) into
-            // the engine's scratch - xn / att in place of their f32 forms, h = silu(gate) * up into h2: no conversion launches, half the bytes
-            auto G = [&](const Tensor & w, const void * xh, float * y, void * yh, const float * bias, const float * resid,
-                         const float * silu_gate = nullptr, hipStream_t s2 = nullptr) {
-                return pm_launch_gemm_q_h(w.type, w.d, nullptr, xh, y, yh, (int) w.K, (int) w.N, T, bias, resid, silu_gate, 0, s2 ? s2 : st);
-            };
-            pm_launch_rmsnorm_q8k(cur, (const float *) L.t[PM355_T_ATTN_NORM].d, nullptr, nullptr, E, T, hp.rms_eps, st, m->xn);
-            // wq | wk | wv: ONE launch over the shared activations, each matrix with its own quant type (mmq_pf.hip jobs; wk / wv alone - N = n_head_kv * head_dim -
-            // filled a fraction of the chip: 212 TFLOP/s as their own launches)
-            int rc;
-            {
-                const Tensor & wq = L.t[PM355_T_WQ], & wk = L.t[PM355_T_WK], & wv = L.t[PM355_T_WV];
-                const pm_gemm_pf_job qkvj[3] = {
-                    {wq.type, (int) wq.N, wq.d, m->q, nullptr, (const float *) L.t[PM355_T_BQ].d, nullptr, nullptr, 0},
-                    {wk.type, (int) wk.N, wk.d, m->k, nullptr, (const float *) L.t[PM355_T_BK].d, nullptr, nullptr, 0},
-                    {wv.type, (int) wv.N, wv.d, m->v, nullptr, (const float *) L.t[PM355_T_BV].d, nullptr, nullptr, 0}};
-                rc = pm_launch_gemm_q_multi(qkvj, 3, nullptr, m->xn, E, T, st);
-            }
-            if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: qkv gemm");
-            const long kvs = (long) hp.n_ctx * Hkv * dh;
-            pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kvs,
-                                    (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st);
-            bool att_h = true;
-            if (pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, nullptr, T, H, Hkv, dh, hp.n_ctx, kq_scale, st, nullptr, 0, 0, 0, 0, m->att)) {
-                att_h = false;
-                if (pm_launch_attn_decode(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st))
-                    return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
-            }
-            float * x_mid = (cur == bufs[0]) ? bufs[1] : bufs[0];
-            if (att_h ? G(L.t[PM355_T_WO], m->att, x_mid, nullptr, nullptr, cur)
-                      : pm_launch_gemm_q_ex(L.t[PM355_T_WO].type, L.t[PM355_T_WO].d, m->att, x_mid, (int) L.t[PM355_T_WO].K, (int) L.t[PM355_T_WO].N, T, nullptr, cur, nullptr, 0, st))
-                return seterr(m, PM355_E_UNSUPPORTED, "prefill: wo gemm");
-            pm_launch_rmsnorm_q8k(x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, nullptr, nullptr, E, T, hp.rms_eps, st, m->xn);
-            {
-                // ffn_gate | ffn_up as ONE launch of pair tiles: h2 = F16(silu(gate) * up) comes out of the up waves' epilogue, the gate result crosses over inside
-                // the workgroup and never reaches HBM (two launches: gate as f32, read back by ffn_up's epilogue - 2 x T x n_ff x 4 bytes per layer)
-                const Tensor & wg = L.t[PM355_T_FFN_GATE], & wu = L.t[PM355_T_FFN_UP];
-                const pm_gemm_pf_job gu[2] = {{wg.type, (int) wg.N, wg.d, nullptr, nullptr, nullptr, nullptr, nullptr, 0},
-                                              {wu.type, (int) wu.N, wu.d, nullptr, m->h2, nullptr, nullptr, nullptr, 0}};
-                static const bool no_pair = [] { const char * e = getenv("PM355_GEMM_PAIR"); return e && e[0] == '0'; }();
-                if (!no_pair && wg.type == wu.type && wg.N == wu.N && pm_gemm_pf_check(wg.type, E, (int) wg.N, T) == 0 && pm_gemm_pf_enabled())
-                    rc = pm_launch_gemm_pf_ex(gu, 2, m->xn, E, T, 1, st);
-                else {
-                    rc = G(wg, m->xn, m->h, nullptr, nullptr, nullptr);
-                    rc |= G(wu, m->xn, nullptr, m->h2, nullptr, nullptr, m->h);                          // h2 = F16(silu(gate) * up), in the epilogue
-                }
-            }
-            if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: gate/up gemm");
-            float * x_next = (il == m->hi - 1 && d_x_out) ? d_x_out : ((x_mid == bufs[0]) ? bufs[1] : bufs[0]);
-            if (G(L.t[PM355_T_FFN_DOWN], m->h2, x_next, nullptr, nullptr, x_mid)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: down gemm");
-            layer_release(m, il, st);
-            cur = x_next;
-            continue;
-        }
-        // attn_norm (+weight), quantized for q/k/v in the same pass when only Q8_K is needed
-        ActQ a = norm_quantize_for(m, cur, (const float *) L.t[PM355_T_ATTN_NORM].d, E, T, qkv, 3, st);
-        int rc = 0;
-        bool prepped = false;
-        const bool small = T >= MMQ_MULTI_MIN_TOKENS && T <= MMQ_MAX_TOKENS && !m->no_mmq && a.k != nullptr;   // (single launches: from MMQ_MIN_TOKENS, in matmul_small)
-        // matrices of one type that share the activations go out as ONE small-batch launch per 32 tokens: wq | wk (| wv), ffn_gate | ffn_up
-        auto multi = [&](std::initializer_list<const Tensor *> ws, std::initializer_list<float *> ys, std::initializer_list<const float *> bs, const pm_qkv_epi * epi = nullptr) {
-            const void * W[3]; int N[3]; float * Y[3]; const float * B[3]; int n = 0;
-            for (const Tensor * w : ws) { W[n] = w->d; N[n] = (int) w->N; ++n; }
-            n = 0; for (float * y : ys) Y[n++] = y;
-            n = 0; for (const float * b : bs) B[n++] = b;
-            const Tensor * w0 = *ws.begin();
-            return pm_launch_mmq_i8_multi(w0->type, n, W, N, Y, B, a.k, (int) w0->K, T, (prepped || a.tab) ? 1 : 0, st, epi);
-        };
-        // RoPE + KV store in the epilogue of the wq | wk | wv launch (NORM rope; the tokens' cos / sin tables were written once for this step): no
-        // rope_kv_store launch. PM355_SMALL_ROPE_EPI=0: the separate launch
-        const long kv_stride = (long) hp.n_ctx * Hkv * dh;
-        const pm_qkv_epi qe = {m->rope_tab, m->d_pos, m->d_ctl, nullptr, kv_stride, L.kc, L.vc, Hkv, dh, hp.n_ctx, m->rope.n_dims, 0, 0};
-        const pm_qkv_epi * epi = small_epi ? &qe : nullptr;
-        bool rope_done = false;
-        const Tensor & wq_ = L.t[PM355_T_WQ], & wk_ = L.t[PM355_T_WK], & wv_ = L.t[PM355_T_WV];
-        const float * bq_ = (const float *) L.t[PM355_T_BQ].d, * bk_ = (const float *) L.t[PM355_T_BK].d, * bv_ = (const float *) L.t[PM355_T_BV].d;
-        bool qkv_done = false;
-        if (small && T <= MMQ_MAX_TOKENS && !m->no_multi && wq_.type == wk_.type) {
-            if (wv_.type == wq_.type) {
-                if (epi && multi({&wq_, &wk_, &wv_}, {m->q, m->k, m->v}, {bq_, bk_, bv_}, epi) == 0) qkv_done = rope_done = true;
-                else if (multi({&wq_, &wk_, &wv_}, {m->q, m->k, m->v}, {bq_, bk_, bv_}) == 0) qkv_done = true;
-            } else if (epi && [&] {
-                           const void * W[2] = {wq_.d, wk_.d}; const int N[2] = {(int) wq_.N, (int) wk_.N}; float * Y[2] = {m->q, m->k}; const float * B[2] = {bq_, bk_};
-                           return wv_.K == wq_.K && pm_launch_mmq_i8_dual(wq_.type, 2, W, N, Y, B, wv_.type, wv_.d, (int) wv_.N, m->v, bv_, a.k, (int) wq_.K, T, (prepped || a.tab) ? 1 : 0, st, epi) == 0;
-                       }()) {
-                qkv_done = rope_done = true;
-            } else if ([&] {        // wv of another K-quant type (Q6_K / Q5_K in the Q4_K_M files): the same grid, its own workgroups (mmq_i8_dual_kernel)
-                           const void * W[2] = {wq_.d, wk_.d}; const int N[2] = {(int) wq_.N, (int) wk_.N}; float * Y[2] = {m->q, m->k}; const float * B[2] = {bq_, bk_};
-                           return wv_.K == wq_.K && pm_launch_mmq_i8_dual(wq_.type, 2, W, N, Y, B, wv_.type, wv_.d, (int) wv_.N, m->v, bv_, a.k, (int) wq_.K, T, (prepped || a.tab) ? 1 : 0, st) == 0;
-                       }()) {
-                qkv_done = true;
-            } else if (multi({&wq_, &wk_}, {m->q, m->k}, {bq_, bk_}) == 0) {
-                prepped = true; qkv_done = true;
-                rc |= matmul_small(m, wv_, a, T, m->v, bv_, nullptr, prepped, st);
-            }
-        }
-        if (!qkv_done) {
-        rc |= matmul_small(m, L.t[PM355_T_WQ], a, T, m->q, (const float *) L.t[PM355_T_BQ].d, nullptr, prepped, st);
-        rc |= matmul_small(m, L.t[PM355_T_WK], a, T, m->k, (const float *) L.t[PM355_T_BK].d, nullptr, prepped, st);
-        rc |= matmul_small(m, L.t[PM355_T_WV], a, T, m->v, (const float *) L.t[PM355_T_BV].d, nullptr, prepped, st);
-        }
-        if (rc) return seterr(m, rc, "decode: qkv gemv");
-        bool fused_attn = false;
-        if (T == 1 && !m->no_fuse)
-            fused_attn = pm_launch_attn_rope_fused(m->q, m->k, m->v, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride,
-                                                   (const float *) m->rope_freqs.d, m->att, H, Hkv, dh, hp.n_ctx, kq_scale, m->rope, st) == 0;
-        if (!fused_attn) {
-        // q rotated AND rounded to F16, every token's K row / V column stored: the attention of a small batch then is the single-token kernel over
-        // cached cells, one workgroup per (head, token) (attn_cached.hip: one barrier up to 64 cells; 11 -> ~4 us per layer at 2..8 tokens)
-        if (!rope_done)
-        pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride,
-                                (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st, 1);
-        // (a shape attn_cached refuses - head_dim other than 64 / 128 / 256, scores beyond 150 KiB of LDS - falls back to attn_decode, which rounds q to
-        //  F16 itself: the pre-rounded rows give it the same bits as raw ones, tests/test_gpu_ops.py::test_small_batch_attention_fallback_...)
-        // (from SMALL_ATTN_MFMA_MIN tokens on: the prompt path's matrix-core kernel - 12 us per layer at 32 tokens against 26 for 2048 small workgroups)
-        if (!(T >= SMALL_ATTN_MFMA_MIN && pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st) == 0))
-        if (pm_launch_attn_cached(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, H, Hkv, dh, hp.n_ctx, kq_scale, st, nullptr, nullptr, 0, 0, 0, T) &&
-            pm_launch_attn_decode(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st))
-            return seterr(m, PM355_E_RANGE, "decode: n_ctx too large for the decode-attention kernel");
-        }
-        const Tensor * wo[1] = {&L.t[PM355_T_WO]};
-        a = quantize_for(m, m->att, Eq, T, wo, 1, st);
-        float * x_mid = (cur == bufs[0]) ? bufs[1] : bufs[0];                 // ffn_inp = wo.att + inpSA
-        prepped = false;
-        if (matmul_small(m, L.t[PM355_T_WO], a, T, x_mid, nullptr, cur, prepped, st)) return seterr(m, PM355_E_UNSUPPORTED, "decode: wo gemv");
-        const Tensor * gu[2] = {&L.t[PM355_T_FFN_GATE], &L.t[PM355_T_FFN_UP]};
-        a = norm_quantize_for(m, x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, E, T, gu, 2, st);
-        if (L.t[PM355_T_FFN_GATE].type != L.t[PM355_T_FFN_UP].type)
-            return seterr(m, PM355_E_UNSUPPORTED, "decode: ffn_gate and ffn_up of different types");
-        const Tensor & wg = L.t[PM355_T_FFN_GATE], & wu = L.t[PM355_T_FFN_UP];
-        bool gu_done = false;
-        // 2 tokens: the pair mat-vec with two column slots - one pass over both matrices, silu(gate) * up in its epilogue (~50 us against 60 for the
-        // two-matrix launch of the matrix-core kernel + the product launch)
-        const bool pair_cols = T == 2 && !m->no_small_cols && wg.type == wu.type && (wg.type == PM_Q4_K || wg.type == PM_Q6_K);
-        if (!pair_cols && small && m->h2 && pm_mmq_i8_check(wg.type, (int) wg.K, (int) wg.N, T) == 0) {
-            // gate and up: one weight pass each for all tokens, then silu(gate) * up (the pair mat-vec would take one launch per token)
-            prepped = false;
-            if (T <= MMQ_MAX_TOKENS && !m->no_multi && wg.type == wu.type && multi({&wg, &wu}, {m->h, m->h2}, {nullptr, nullptr}) == 0) gu_done = true;
-            else if (T >= MMQ_MIN_TOKENS) {
-                if (matmul_small(m, wg, a, T, m->h, nullptr, nullptr, prepped, st) || matmul_small(m, wu, a, T, m->h2, nullptr, nullptr, prepped, st))
-                    return seterr(m, PM355_E_UNSUPPORTED, "decode: gate/up small-batch mat-mul");
-                gu_done = true;
-            }
-        }
-        if (!gu_done)
-        if (gemv(L.t[PM355_T_FFN_GATE], &L.t[PM355_T_FFN_UP], a, T, m->h, nullptr, nullptr, st)) return seterr(m, PM355_E_UNSUPPORTED, "decode: gate/up gemv");
-        const Tensor * dn[1] = {&L.t[PM355_T_FFN_DOWN]};
-        if (gu_done && L.t[PM355_T_FFN_DOWN].type != PM_Q8_0) {
-            // silu(gate) * up goes straight into the Q8_K rows (and activation tables) ffn_down reads: no f32 product, one launch less
-            const pm_q8k_tables tb = mmq_tables(m, F, T, st);
-            pm_launch_silu_mul_q8k(m->h, m->h2, m->aq_k, F, T, st, tb);
-            a = ActQ(); a.k = m->aq_k; a.tab = tb.base != nullptr;
-        } else {
-            // Q8_0 ffn_down (n_ff no multiple of 256) on the small-batch mat-mul: silu(gate) * up quantized straight into its activation tables - one launch
-            // instead of silu_mul, quantize_q80 and the mat-mul's table prologue
-            const Tensor & wd = L.t[PM355_T_FFN_DOWN];
-            void * tab = nullptr; size_t qb = 0, db = 0;
-            if (gu_done && T >= MMQ_MIN_TOKENS && T <= MMQ_MAX_TOKENS && !m->no_mmq && !m->no_multi && pm_mmq_i8_check(wd.type, (int) wd.K, (int) wd.N, T) == 0 &&
-                pm_mmq_i8_q80_tables((int) wd.K, st, &tab, &qb, &db) == 0) {
-                pm_launch_silu_mul_q80_tab(m->h, m->h2, tab, qb, db, F, T, st);
-                float * x_nx = (il == m->hi - 1 && d_x_out) ? d_x_out : ((x_mid == bufs[0]) ? bufs[1] : bufs[0]);
-                if (pm_launch_mmq_i8(wd.type, wd.d, nullptr, nullptr, x_nx, (int) wd.K, (int) wd.N, T, nullptr, x_mid, 1, st)) return seterr(m, PM355_E_UNSUPPORTED, "decode: down mat-mul");
-                layer_release(m, il, st);
-                cur = x_nx;
-                continue;
-            }
-            if (gu_done) pm_launch_silu_mul(m->h, m->h2, m->h, (long) T * F, st);
-            a = quantize_for(m, m->h, F, T, dn, 1, st);
-        }
-        // `cur` is dead after the wo GEMV consumed it as residual, so the other scratch buffer can be reused
+        const Layer L = layer_acquire(m, il, st);
+        // `cur` is dead after the wo mat-mul consumed it as residual, so the other scratch buffer can be reused
+        float * x_mid = (cur == bufs[0]) ? bufs[1] : bufs[0];
         float * x_next = (il == m->hi - 1 && d_x_out) ? d_x_out : ((x_mid == bufs[0]) ? bufs[1] : bufs[0]);
-        prepped = false;
-        if (matmul_small(m, L.t[PM355_T_FFN_DOWN], a, T, x_next, nullptr, x_mid, prepped, st)) return seterr(m, PM355_E_UNSUPPORTED, "decode: down gemv");
+        const LayerPath path = layer_path(m, L, T);
+        const int rc = path == LayerPath::prompt_i8  ? layer_prompt_i8(m, L, T, cur, x_mid, x_next, st)
+                     : path == LayerPath::prompt_f16 ? layer_prompt_f16(m, L, T, cur, x_mid, x_next, st)
+                                                     : layer_small(m, L, T, cur, x_mid, x_next, st);
+        if (rc) return rc;
         layer_release(m, il, st);
         cur = x_next;
     }
@@ -879,10 +880,7 @@ pm355_model * pm355_model_new(const pm355_hparams * hp, int lo, int hi, int flag
     m->rope.freq_base = hp->rope_freq_base; m->rope.freq_scale = hp->rope_freq_scale;
     m->rope.ext_factor = 0.0f; m->rope.attn_factor = 1.0f; m->rope.beta_fast = 32.0f; m->rope.beta_slow = 1.0f;
     pm_rope_params(m->rope);
-    { const char * e = getenv("PM355_NO_FUSE"); m->no_fuse = e && e[0] == '1'; }
     { const char * e = getenv("PM355_SMALL_ROPE_EPI"); m->no_small_epi = e && e[0] == '0'; }
-    { const char * e = getenv("PM355_SMALL_COLS"); m->no_small_cols = e && e[0] == '0'; }   // A/B: 2..4-token steps without the round-4 multi-column choices
-    { const char * e = getenv("PM355_NO_MMQ_MULTI"); m->no_multi = e && e[0] == '1'; }   // small batches: one launch per matrix (A/B of the multi-job launches)
     { const char * e = getenv("PM355_NO_MMQ_I8"); m->no_mmq = e && e[0] == '1'; }     // 4..64-token batches: mat-vec columns / F16 GEMM from 16 (the round-1 paths)
     { const char * e = getenv("PM355_QKV_EPI"); m->qkv_epi = !(e && e[0] == '0'); }
     { const char * e = getenv("PM355_PROMPT_I8"); m->no_big = !(e && e[0] == '1'); }
