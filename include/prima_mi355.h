@@ -31,7 +31,7 @@ extern "C" {
 #define PM355_API __attribute__((visibility("default")))
 
 /* ggml type ids, identical to enum ggml_type (ggml/include/ggml.h:356-372) */
-enum { PM355_TYPE_F32 = 0, PM355_TYPE_F16 = 1, PM355_TYPE_Q8_0 = 8, PM355_TYPE_Q4_K = 12,
+enum { PM355_TYPE_F32 = 0, PM355_TYPE_F16 = 1, PM355_TYPE_Q5_0 = 6, PM355_TYPE_Q8_0 = 8, PM355_TYPE_Q4_K = 12,
        PM355_TYPE_Q5_K = 13, PM355_TYPE_Q6_K = 14 };
 
 enum { PM355_OK = 0, PM355_E_UNSUPPORTED = -1, PM355_E_SHAPE = -2, PM355_E_ALIGN = -3, PM355_E_RANGE = -4,
@@ -104,11 +104,11 @@ PM355_API uint64_t pm355_uploader_bytes(const pm355_uploader * u);
 /* ---- weight layout ------------------------------------------------------------------------------ */
 /* bytes of one row of K weights == ggml_row_size(type, K) (ggml/src/ggml.c:3579) */
 PM355_API size_t pm355_row_size(int type, int64_t K);
-/* row stride of the HBM layout: == pm355_row_size except Q6_K / Q8_0 with K % 2048 != 0 (row-SoA scale stream padded
+/* row stride of the HBM layout: == pm355_row_size except Q6_K / Q8_0 with K % 2048 != 0 and Q5_0 with K % 256 != 0 (row-SoA streams padded
  * to 16 B). A tensor of N rows occupies N * pm355_row_stride bytes in HBM (the plug-in's get_alloc_size). */
 PM355_API size_t pm355_row_stride(int type, int64_t K);
-/* Row-local re-ordering GGUF block order <-> HBM order (identity for F32/F16/Q4_K/Q5_K, row-SoA for
- * Q6_K/Q8_0; see prima_cpp_amd/csrc/repack.hip). src and dst are DEVICE pointers and must not overlap; the GGUF-order
+/* Row-local re-ordering GGUF block order <-> HBM order (identity for F32/F16/Q5_K, row-SoA for
+ * Q4_K/Q6_K/Q8_0/Q5_0 - Q5_0: qs[nb][16] | qh[nb][4] | d[nb], qh and d streams padded to 16 bytes; see prima_cpp_amd/csrc/repack.hip). src and dst are DEVICE pointers and must not overlap; the GGUF-order
  * side has rows pm355_row_size apart, the HBM side pm355_row_stride apart.
  * to_device_layout=1 is what set_tensor does after the H2D copy; 0 is what get_tensor does before D2H. */
 PM355_API int    pm355_repack_rows(int type, const void * src, void * dst, int64_t K, int64_t nrows,

@@ -339,7 +339,7 @@ int pm355_mul_mat_vec_q_dbg(int type, const void * W, int64_t K, int64_t N, cons
 }
 
 int pm355_get_rows(int type, const void * table, int64_t K, const int32_t * d_tokens, int n_tokens, float * out, pm355_stream_t st) {
-    if (!pm_weight_row_bytes(type, K)) return fail(PM355_E_UNSUPPORTED, "get_rows: type");
+    if (!pm_weight_row_bytes(type, K) || !pm_embed_type_ok(type)) return fail(PM355_E_UNSUPPORTED, "get_rows: type (Q5_0 embedding rows are not served)");
     pm_launch_embed(type, table, (int) K, d_tokens, n_tokens, out, S(st));
     HIP_TRY(hipGetLastError());
     return 0;

@@ -196,6 +196,8 @@ __global__ void fix_scales_kernel(int type, uint8_t * dst, long nb_total, long n
         *(uint16_t *) (r + pm_q6k_d_off((uint32_t) nb_row, (uint32_t) bi)) = f2h(u * scale / 2048.f);
     } else if (type == PM_Q8_0) {
         ((uint16_t *) (r + nb_row * 32))[bi] = f2h(u * scale / 64.f);
+    } else if (type == PM_Q5_0) {                                     // q - 16 in [-16, 15]: about the spread of Q8_0's q / 8
+        ((uint16_t *) (r + pm_q50_d_off((uint32_t) nb_row)))[bi] = f2h(u * scale / 8.f);
     }
 }
 __global__ void fill_random_f32_kernel(float * dst, long n, uint64_t seed, float mean, float amp) {
@@ -216,7 +218,7 @@ void pm_launch_fill_random_blocks(int type, void * dst, int64_t K, int64_t nrows
     if (type == PM_F32) { hipLaunchKernelGGL(fill_random_f32_kernel, dim3((unsigned) ((n / 4 + 255) / 256)), dim3(256), 0, st, (float *) dst, n / 4, seed, 0.0f, scale); return; }
     if (type == PM_F16) { hipLaunchKernelGGL(fill_random_f16_kernel, dim3((unsigned) ((n / 2 + 255) / 256)), dim3(256), 0, st, (uint16_t *) dst, n / 2, seed, scale); return; }
     const long nd = (n + 3) / 4;
-    const long nb_row = type == PM_Q8_0 ? K / 32 : K / 256;
+    const long nb_row = pm_q80_family(type) ? K / 32 : K / 256;
     hipLaunchKernelGGL(fill_random_blocks_kernel, dim3((unsigned) ((nd + 255) / 256)), dim3(256), 0, st, type, (uint32_t *) dst, nd, nb_row * nrows, nb_row, seed, scale);
     hipLaunchKernelGGL(fix_scales_kernel, dim3((unsigned) ((nb_row * nrows + 255) / 256)), dim3(256), 0, st, type, (uint8_t *) dst, nb_row * nrows, nb_row, (long) rb, seed, scale);
 }
@@ -293,7 +295,7 @@ pm_q8k_tables mmq_tables(const pm355_model * m, int K, int T, hipStream_t st) {
 }
 ActQ quantize_for(pm355_model * m, const float * src, int K, int T, const Tensor * const * ws, int nw, hipStream_t st) {
     ActQ a; bool need_k = false, need_0 = false;
-    for (int i = 0; i < nw; ++i) if (ws[i] && ws[i]->d) { if (ws[i]->type == PM_Q8_0) need_0 = true; else need_k = true; }
+    for (int i = 0; i < nw; ++i) if (ws[i] && ws[i]->d) { if (pm_q80_family(ws[i]->type)) need_0 = true; else need_k = true; }
     if (need_k) { const pm_q8k_tables tb = mmq_tables(m, K, T, st); pm_launch_quantize_q8k(src, m->aq_k, K, T, st, tb); a.k = m->aq_k; a.tab = tb.base != nullptr; }
     if (need_0) { pm_launch_quantize_q80(src, m->aq_0, K, T, st); a.z = m->aq_0; }
     return a;
@@ -301,7 +303,7 @@ ActQ quantize_for(pm355_model * m, const float * src, int K, int T, const Tensor
 
 ActQ norm_quantize_for(pm355_model * m, const float * src, const float * w, int K, int T, const Tensor * const * ws, int nw, hipStream_t st) {
     bool need_0 = false;
-    for (int i = 0; i < nw; ++i) if (ws[i] && ws[i]->d && ws[i]->type == PM_Q8_0) need_0 = true;
+    for (int i = 0; i < nw; ++i) if (ws[i] && ws[i]->d && pm_q80_family(ws[i]->type)) need_0 = true;
     if (!need_0) {
         const pm_q8k_tables tb = mmq_tables(m, K, T, st);
         pm_launch_rmsnorm_q8k(src, w, nullptr, m->aq_k, K, T, m->hp.rms_eps, st, nullptr, tb);
@@ -314,7 +316,7 @@ ActQ norm_quantize_for(pm355_model * m, const float * src, const float * w, int 
 int gemv(const Tensor & w, const Tensor * w2, const ActQ & a, int T, float * y, const float * bias, const float * resid, hipStream_t st) {
     pm_gemv_args g = {};
     g.type = w.type; g.K = (int) w.K; g.N = (int) w.N; g.W = w.d; g.W2 = w2 ? w2->d : nullptr;
-    g.xq = w.type == PM_Q8_0 ? a.z : a.k; g.ncols = T; g.y = y; g.y_stride = (size_t) w.N; g.bias = bias; g.resid = resid;
+    g.xq = pm_q80_family(w.type) ? a.z : a.k; g.ncols = T; g.y = y; g.y_stride = (size_t) w.N; g.bias = bias; g.resid = resid;
     return pm_launch_gemv(g, st);
 }
 
@@ -324,7 +326,7 @@ int gemv(const Tensor & w, const Tensor * w2, const ActQ & a, int T, float * y, 
 int matmul_small(pm355_model * m, const Tensor & w, const ActQ & a, int T, float * y, const float * bias, const float * resid, bool & prepped, hipStream_t st) {
     // (3 / 4 tokens on the 4-slot multi-column mat-vec - two rows per activation fetch: ffn_down Q6_K 46 us - measured against this kernel once it had
     //  its operand-ordered activation table (54 us without the prologue launch): 177 vs 172 us per layer, so the matrix-core kernel keeps them)
-    const bool q80 = w.type == PM_Q8_0;                  // Q8_0 weights take Q8_0 activations; the kernel builds their tables per call
+    const bool q80 = pm_q80_family(w.type);              // Q8_0 / Q5_0 weights take Q8_0 activations; the kernel builds their tables per call
     const void * xa = q80 ? a.z : a.k;
     if (T >= MMQ_MIN_TOKENS && T <= MMQ_MAX_TOKENS && !m->no_mmq && xa && pm_mmq_i8_check(w.type, (int) w.K, (int) w.N, T) == 0) {
         const int rc = pm_launch_mmq_i8(w.type, w.d, xa, nullptr, y, (int) w.K, (int) w.N, T, bias, resid, q80 ? 0 : ((prepped || a.tab) ? 1 : 0), st);
@@ -579,9 +581,10 @@ LayerPath layer_path(const pm355_model * m, const Layer & L, int T) {
     bool small_ok = !m->no_mmq && small_attn_ok;              // ... and unless one of the layer's large matrices has a type neither small-batch path serves
     for (int k : {PM355_T_WQ, PM355_T_WO, PM355_T_FFN_GATE, PM355_T_FFN_UP, PM355_T_FFN_DOWN}) {
         // Q4_K / Q5_K / Q6_K and (round 4) Q8_0 - Qwen2.5-72B's ffn_down: 29568 % 256 != 0, src/llama.cpp:19547 - on the integer matrix cores
-        // (mmq_i8.hip; Q8_0 with Q8_0 activations = ggml_vec_dot_q8_0_q8_0's arithmetic); a Q8_0 shape it does not serve falls back to the multi-column mat-vec
+        // (mmq_i8.hip; Q8_0 with Q8_0 activations = ggml_vec_dot_q8_0_q8_0's arithmetic; Q5_0, the Q4_K_M files' fallback, likewise); a Q8_0 / Q5_0
+        // shape it does not serve falls back to the multi-column mat-vec
         const bool served = pm_mmq_i8_check(L.t[k].type, (int) L.t[k].K, (int) L.t[k].N, std::min(T, MMQ_MAX_TOKENS)) == 0;
-        small_ok = small_ok && (served || L.t[k].type == PM_Q8_0);
+        small_ok = small_ok && (served || pm_q80_family(L.t[k].type));
     }
     // prompts: every large matrix the integer kernel serves (Q4_K / Q6_K, K % 1024 == 0) runs on Q8_K activations with the CPU reference's
     // arithmetic; wv alone may stay on the F16 GEMM (Llama-3-70B Q4_K_M: Q5_K in half the layers, src/llama.cpp:19360-19373)
@@ -774,13 +777,13 @@ int small_ffn(pm355_model * m, const Layer & L, int T, bool small, const float *
         }
     }
     if (!gu_done && gemv(wg, &wu, a, T, m->h, nullptr, nullptr, st)) return seterr(m, PM355_E_UNSUPPORTED, "decode: gate/up gemv");
-    if (gu_done && wd.type != PM_Q8_0) {
+    if (gu_done && !pm_q80_family(wd.type)) {
         // silu(gate) * up goes straight into the Q8_K rows (and activation tables) ffn_down reads: no f32 product, one launch less
         const pm_q8k_tables tb = mmq_tables(m, F, T, st);
         pm_launch_silu_mul_q8k(m->h, m->h2, m->aq_k, F, T, st, tb);
         a = ActQ(); a.k = m->aq_k; a.tab = tb.base != nullptr;
     } else {
-        // Q8_0 ffn_down (n_ff no multiple of 256) on the small-batch mat-mul: silu(gate) * up quantized straight into its activation tables - one launch
+        // Q8_0 / Q5_0 ffn_down (n_ff no multiple of 256) on the small-batch mat-mul: silu(gate) * up quantized straight into its activation tables - one launch
         // instead of silu_mul, quantize_q80 and the mat-mul's table prologue
         void * tab = nullptr; size_t qb = 0, db = 0;
         if (gu_done && T >= MMQ_MIN_TOKENS && pm_mmq_i8_check(wd.type, (int) wd.K, (int) wd.N, T) == 0 && pm_mmq_i8_q80_tables((int) wd.K, st, &tab, &qb, &db) == 0) {
@@ -944,6 +947,7 @@ int pm355_model_set_tensor(pm355_model * m, int kind, int layer, int type, const
     (void) hipGetLastError();
     Tensor * t = tensor_slot(m, kind, layer);
     if (!t) return seterr(m, PM355_E_RANGE, "set_tensor: tensor not in this window");
+    if (kind == PM355_T_TOK_EMBD && !pm_embed_type_ok(type)) return seterr(m, PM355_E_UNSUPPORTED, "set_tensor: token embedding type (Q5_0 embedding rows are not served)");
     int rc = alloc_tensor(m, t, kind, type);
     if (rc) return seterr(m, rc, "set_tensor: alloc");
     if (nbytes != t->bytes) return seterr(m, PM355_E_SHAPE, "set_tensor: byte size does not match type/shape");
@@ -959,6 +963,7 @@ int pm355_model_fill_tensor(pm355_model * m, int kind, int layer, int type, uint
     (void) hipGetLastError();
     Tensor * t = tensor_slot(m, kind, layer);
     if (!t) return seterr(m, PM355_E_RANGE, "fill_tensor: tensor not in this window");
+    if (kind == PM355_T_TOK_EMBD && !pm_embed_type_ok(type)) return seterr(m, PM355_E_UNSUPPORTED, "fill_tensor: token embedding type (Q5_0 embedding rows are not served)");
     int rc = alloc_tensor(m, t, kind, type);
     if (rc) return seterr(m, rc, "fill_tensor: alloc");
     if (!is_matrix(kind)) {

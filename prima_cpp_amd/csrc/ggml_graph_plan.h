@@ -102,8 +102,10 @@ struct ptr_count {
 inline bool is_view_op(enum ggml_op op) {
     return op == GGML_OP_NONE || op == GGML_OP_RESHAPE || op == GGML_OP_VIEW || op == GGML_OP_PERMUTE || op == GGML_OP_TRANSPOSE;
 }
-inline bool quant_matvec_type(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0; }
-inline bool soa_type(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0; }
+inline bool quant_matvec_type(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q5_0; }
+inline bool soa_type(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q5_0; }
+// weights whose vec_dot_type is Q8_0 (32-value blocks: K % 32)
+inline bool q80_act_type(enum ggml_type t) { return t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q5_0; }
 inline bool f32_vec(const ggml_tensor * t, int64_t n) {           // contiguous f32 [n, 1, 1, 1]
     return t && t->type == GGML_TYPE_F32 && t->ne[0] == n && t->ne[1] == 1 && t->ne[2] == 1 && t->ne[3] == 1 && t->nb[0] == 4;
 }
@@ -142,7 +144,9 @@ inline void graph_fingerprint(struct ggml_cgraph * g, graph_fp & out) {
         const bool cell_view = t->op == GGML_OP_VIEW && base != t->data;
         if (!cell_view) for (int k = 0; k < 16; k += 2) mix(((uint64_t) (uint32_t) t->op_params[k] << 32) | (uint32_t) t->op_params[k + 1]);
         for (int k = 0; k < 4; ++k) { mix((uint64_t) t->ne[k]); mix((uint64_t) t->nb[k]); }
-        for (int k = 0; k < 3; ++k) mix(t->src[k] ? (uint64_t) (uintptr_t) fp_base(t->src[k]) : 0);
+        // sources by address AND type (bits 52+; addresses stay below 2^48): a weight leaf is no node of its own, and a graph that re-uses the
+        // addresses of the previous one with another weight type (test-backend-ops: MUL_MAT q5_0 then q8_0 on the same buffers) must not match its plan
+        for (int k = 0; k < 3; ++k) mix(t->src[k] ? (uint64_t) (uintptr_t) fp_base(t->src[k]) ^ ((uint64_t) (uint32_t) t->src[k]->type << 52) : 0);
     }
     out.h0 = a; out.h1 = b; out.n = n;
 }
@@ -243,7 +247,7 @@ private:
         if (!t || t->op != GGML_OP_MUL_MAT) return false;
         const ggml_tensor * w = t->src[0], * x = t->src[1];
         if (!w || !x || !quant_matvec_type(w->type) || w->view_src || !ggml_is_contiguous(w) || w->ne[2] != 1 || w->ne[3] != 1) return false;
-        if (w->ne[0] % (w->type == GGML_TYPE_Q8_0 ? 32 : 256) || w->ne[0] > 131072) return false;
+        if (w->ne[0] % (q80_act_type(w->type) ? 32 : 256) || w->ne[0] > 131072) return false;
         if (!f32_vec(x, w->ne[0]) || !f32_vec(t, w->ne[1])) return false;
         return !x_expected || x == x_expected;
     }

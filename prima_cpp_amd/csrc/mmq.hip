@@ -2,7 +2,7 @@
 //
 // Replaces ggml_compute_forward_mul_mat (ggml/src/ggml.c:12377) for n_tokens >= 16 (what the reference's CUDA plug-in
 // serves with mul_mat_q / dequantize + cuBLAS, ggml-cuda/mmq.cuh:2583, convert.cu:190-279):
-//     Y[t][n] = sum_k W[n][k] * X[t][k]           W: Q4_K / Q5_K / Q6_K / Q8_0 rows in the HBM layout of repack.hip
+//     Y[t][n] = sum_k W[n][k] * X[t][k]           W: Q4_K / Q5_K / Q6_K / Q8_0 / Q5_0 rows in the HBM layout of repack.hip
 // Design: weights are read from HBM exactly once per 256-token tile, dequantized on the fly into an F16 LDS tile (packed-F16
 // math for Q4_K / Q6_K, see convert_w_h; f32 math = the exact d*sc*q - dmin*m of dequantize_row_* rounded to F16 for the
 // other types); the activations are converted F32 -> F16
@@ -36,6 +36,14 @@ __device__ __forceinline__ void fetch_w(const uint8_t * row, int K, int k0, int 
         w.r[0] = *(const u32x4 *) (row + part * (K / 2) + (k0 >> 1));
         return;
     }
+    if (TYPE == PM_Q5_0) {                                             // row-SoA: qs[nb][16] | qh[nb][4] | half d[nb] (pm355_device.h pm_q50_*)
+        const uint32_t nb = (uint32_t) K / 32u, b = (uint32_t) k0 >> 5;
+        w.r[0] = *(const u32x4 *) (row + b * 16u);                     // the block's 16 qs bytes: part 0 = low nibbles, part 1 = high nibbles
+        w.r[1][0] = *(const uint32_t *) (row + pm_q50_qh_off(nb) + b * 4u) >> (16 * part);   // the 16 high bits of this part
+        w.r[1][1] = (uint32_t) part;
+        w.s = ((const uint16_t *) (row + pm_q50_d_off(nb)))[b];
+        return;
+    }
     const int b = k0 >> 8, s = (k0 & 255) >> 5;                         // super-block, 32-value sub-block
     if (TYPE == PM_Q4_K || TYPE == PM_Q5_K) {
         // Q4_K row-SoA: qa[U][16] | qb[U][16] | hdr[nb][16] (unit = block*4 + s/2);  Q5_K native 176-byte blocks
@@ -64,6 +72,18 @@ __device__ __forceinline__ void convert_w(const RawW & w, int k0, float (&o)[16]
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[4 * i + j] = (float) (int8_t) (w.r[0][i] >> (8 * j)) * d;
+        return;
+    }
+    if (TYPE == PM_Q5_0) {                                             // dequantize_row_q5_0 (ggml-quants.c:1563): (float) (q - 16) * d
+        const float d = h2f((uint16_t) w.s);
+        const int sh = 4 * (int) w.r[1][1];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = (int) (((w.r[0][i] >> (8 * j + sh)) & 0xFu) | (((w.r[1][0] >> (4 * i + j)) & 1u) << 4)) - 16;
+                o[4 * i + j] = (float) v * d;
+            }
         return;
     }
     const int s = (k0 & 255) >> 5;
@@ -582,8 +602,8 @@ int pm_launch_gemm_q_ex(int type, const void * W, const float * X, float * Y, in
 // (the rounding the next GEMM's conversion pass would apply) and Y is not written.
 int pm_launch_gemm_q_h(int type, const void * W, const float * X, const void * x_f16, float * Y, void * y_f16, int K, int N, int T,
                        const float * bias, const float * resid, const float * silu_gate, int reuse_x, hipStream_t st) {
-    if (K % 64 || (type != PM_Q8_0 && K % 256) || N % 4) return -2;
-    if (type != PM_Q4_K && type != PM_Q5_K && type != PM_Q6_K && type != PM_Q8_0) return -1;
+    if (K % 64 || (!pm_q80_family(type) && K % 256) || N % 4) return -2;
+    if (type != PM_Q4_K && type != PM_Q5_K && type != PM_Q6_K && type != PM_Q8_0 && type != PM_Q5_0) return -1;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
     const size_t need = (size_t) T * K;
@@ -620,6 +640,7 @@ int pm_launch_gemm_q_h(int type, const void * W, const float * X, const void * x
             case PM_Q4_K: go2(gemm_q_f16_kernel2<PM_Q4_K>); break;
             case PM_Q5_K: go2(gemm_q_f16_kernel2<PM_Q5_K>); break;
             case PM_Q6_K: go2(gemm_q_f16_kernel2<PM_Q6_K>); break;
+            case PM_Q5_0: go2(gemm_q_f16_kernel2<PM_Q5_0>); break;
             default:      go2(gemm_q_f16_kernel2<PM_Q8_0>); break;
         }
     };
@@ -635,6 +656,7 @@ int pm_launch_gemm_q_h(int type, const void * W, const float * X, const void * x
             case PM_Q4_K: go(gemm_q_f16_kernel<PM_Q4_K>); break;
             case PM_Q5_K: go(gemm_q_f16_kernel<PM_Q5_K>); break;
             case PM_Q6_K: go(gemm_q_f16_kernel<PM_Q6_K>); break;
+            case PM_Q5_0: go(gemm_q_f16_kernel<PM_Q5_0>); break;
             default:      go(gemm_q_f16_kernel<PM_Q8_0>); break;
         }
     };
@@ -678,7 +700,7 @@ int pm_launch_gemm_q_multi(const pm_gemm_pf_job * jobs, int njobs, const float *
         if (!seen) ty[nty++] = jobs[j].type;
     }
     all_pf = all_pf && nty <= 2;
-    if (nty == 2 && (ty[0] == PM_Q8_0 || ty[1] == PM_Q8_0)) all_pf = false;      // (Q8_0 goes as a launch of its own)
+    if (nty == 2 && (pm_q80_family(ty[0]) || pm_q80_family(ty[1]))) all_pf = false;      // (Q8_0 / Q5_0 go as launches of their own)
     int rc = 0;
     for (int j = 0; j < njobs; ++j) {
         if (all_pf && j > 0) break;

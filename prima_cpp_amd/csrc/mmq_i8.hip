@@ -401,6 +401,67 @@ template <> struct MT<PM_Q8_0> {
     }
 };
 
+// ---------------------------------------------------------------- Q5_0: row = qs[nb][16] | qh[nb][4] | d[nb] (f16), nb = K / 32 (pm355_device.h) ------
+// Q8_0 activations (ggml_vec_dot_q5_0_q8_0, ggml-quants.c:4789: sumi per block, times d_w * d_a): Q8_0's tile plan. A step = 8 blocks per row: 128 bytes of
+// qs (the tile loader's stream a), 32 bytes of qh and 16 bytes of d (the per-row "header" tile: qh | d = exactly PITCH_H). Lane (r, g) of the B operand
+// takes nibble plane g of the block's qs (weights 16 g .. + 15) with qh bits 16 g .. + 15 as bit 4 and subtracts 16 per byte: the int8 weights of the
+// reference, one 32-k MFMA per block. Blocks past the row: clamped / padding bytes against zero activations and scales (as Q8_0).
+template <> struct MT<PM_Q5_0> {
+    static constexpr int QA = 0, HD = 32 * PITCH, DS = HD + 32 * PITCH_H, WAVE_LDS = DS + 1024;
+    struct B { u32x4 qa[4], h, dd, ds; };
+    struct A { u32x4 q[4]; };
+    template <class RW>
+    static __device__ __forceinline__ void issue_b_part(B & b, const RW & rw, int nb /*blocks per row*/, int pr, int lane, int n) {
+        const uint32_t u = (uint32_t) min(8 * pr + (lane & 7), nb - 1);
+        b.qa[n] = ld_nt16(rw.at(n, u * 16u));
+        // the step's 32 qh bytes (two lanes per row) and 8 d (both lanes; the even one stashes them): cached, the row padding keeps the last step inside the row
+        if (n == 0) b.h = ld_c16(rw.at_h(pm_q50_qh_off((uint32_t) nb) + (uint32_t) pr * 32u + (uint32_t) (lane & 1) * 16u));
+        if (n == 1) b.dd = ld_c16(rw.at_h(pm_q50_d_off((uint32_t) nb) + (uint32_t) pr * 16u));
+    }
+    static __device__ __forceinline__ void issue_ds(B & b, const ActSrc & x, int pr) { b.ds = __builtin_bit_cast(u32x4, x.ld_d4(8 * pr, 0)); }
+    static __device__ __forceinline__ void stash(const B & b, uint8_t * L, int lane) {
+        const int rr = lane >> 3, c = lane & 7;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) *(u32x4 *) (L + QA + (rr + 8 * n) * PITCH + c * 16) = b.qa[n];
+        *(u32x4 *) (L + HD + (lane >> 1) * PITCH_H + (lane & 1) * 16) = b.h;
+        if ((lane & 1) == 0) *(u32x4 *) (L + HD + (lane >> 1) * PITCH_H + 32) = b.dd;
+        *(u32x4 *) (L + DS + lane * 16) = b.ds;
+    }
+    template <int NV>
+    static __device__ __forceinline__ void issue_a(A & a, const ActSrc & x, int sb) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a.q[j] = x.ld_blk(4 * sb + j);
+    }
+    template <int NV, class F>
+    static __device__ __forceinline__ void compute(const A & a, const uint8_t * L, int sbi, int r, int g, const float *, int t_off, f32x16 & out, F && between) {
+        const i32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        const u32x4 qh4 = *(const u32x4 *) (L + HD + r * PITCH_H + sbi * 16);           // this row's qh of the four blocks
+        const u32x2 d4 = *(const u32x2 *) (L + HD + r * PITCH_H + 32 + sbi * 8);        // and their scales (f16)
+        const float * ds = (const float *) (L + DS) + t_off;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            between(j);
+            const u32x4 qs = *(const u32x4 *) (L + QA + r * PITCH + (4 * sbi + j) * 16);
+            u32x4 w;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                // 5-bit q = nibble | high bit << 4; q - 16 as int8: flip bit 4, then copy it into bits 5..7 (sign extension of the 5-bit two's complement)
+                const uint32_t t = (((qs[i] >> (4 * g)) & 0x0F0F0F0Fu) | (((qh4[j] >> (16 * g + 4 * i)) & 0xFu) * 0x00204081u & 0x01010101u) << 4) ^ 0x10101010u;
+                w[i] = t | ((t & 0x10101010u) * 14u);
+            }
+            const uint32_t hb = (d4[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+            const float dw = (hb & 0x7C00u) == 0x7C00u ? 0.0f : h2f((uint16_t) hb);       // (a block past the row: whatever the padding holds, times zero)
+            const i32x16 acc = mfma_i8x32(a.q[j], w, zero);
+#pragma unroll
+            for (int q = 0; q < NV / 4; ++q) {
+                const f32x4 yd = *(const f32x4 *) (ds + (4 * sbi + j) * 32 + 8 * q + 4 * g);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) out[4 * q + i] = fmaf((float) acc[4 * q + i], dw * yd[i], out[4 * q + i]);
+            }
+        }
+    }
+};
+
 // ABL (measurement only, PM355_MMQ_ABL): 1 = no activation loads in the loop, 2 = no weight loads in the loop, 4 = no MFMA / VALU work
 // the work of workgroup w of G on the launch p (its own grid, or one part of a two-part launch)
 // EPI: the wq | wk | wv epilogue (MmqP::e_*) is compiled in - instantiations of their own: carried by every kernel as a run-time switch it cost the launches
@@ -409,7 +470,7 @@ template <int TYPE, int NV, int ABL, bool MJ, bool EPI = false>  // NV result re
 __device__ __forceinline__ void mmq_i8_body(const MmqP & p, const int w, const int G, uint8_t * smem) {
     typedef MT<TYPE> M;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;   // (a scalar: the K slice, the loop counters and the buffer loads' scalar offsets derive from it)
-    constexpr bool Q80 = TYPE == PM_Q8_0;                         // 32-value blocks: "super-block" = 4 blocks, no scale table in LDS (scales travel with the operands)
+    constexpr bool Q80 = pm_q80_family(TYPE);                     // 32-value blocks (Q8_0, Q5_0): "super-block" = 4 blocks, no scale table in LDS (scales travel with the operands)
     const int nsb = Q80 ? (p.K + 127) / 128 : p.K / 256, npairs = (nsb + 1) >> 1;
     const int nbw = Q80 ? p.K / 32 : nsb;                         // what the tile loader counts in: blocks of the row
     float * dTl = (float *) smem;                                 // activation scales [nsb + 1][32] (0 for token slots >= T; last row all 0)
@@ -642,14 +703,15 @@ std::mutex g_scr_mu;
 
 size_t pm_mmq_i8_lds_bytes(int type, int K) {
     if (type == PM_Q8_0) return (size_t) NWAVE * MT<PM_Q8_0>::WAVE_LDS;
+    if (type == PM_Q5_0) return (size_t) NWAVE * MT<PM_Q5_0>::WAVE_LDS;
     const size_t w = type == PM_Q4_K ? MT<PM_Q4_K>::WAVE_LDS : type == PM_Q5_K ? MT<PM_Q5_K>::WAVE_LDS : MT<PM_Q6_K>::WAVE_LDS;
     return (size_t) (K / 256 + 1) * 128 + NWAVE * w;
 }
 
 // 0 when pm_launch_mmq_i8 serves this shape
 int pm_mmq_i8_check(int type, int K, int N, int T) {
-    if (type != PM_Q4_K && type != PM_Q5_K && type != PM_Q6_K && type != PM_Q8_0) return -1;
-    if (type == PM_Q8_0) return (T < 1 || T > 64 || K % 32 || K < 512 || N < 1) ? -2 : 0;
+    if (type != PM_Q4_K && type != PM_Q5_K && type != PM_Q6_K && type != PM_Q8_0 && type != PM_Q5_0) return -1;
+    if (pm_q80_family(type)) return (T < 1 || T > 64 || K % 32 || K < 512 || N < 1) ? -2 : 0;
     if (T < 1 || T > 64 || K % 256 || K < 512 || N < 1) return -2;
     if (pm_mmq_i8_lds_bytes(type, K) > 150 * 1024) return -4;
     return 0;
@@ -699,7 +761,7 @@ void launch_prep(const Scr * sc, const void * xq, int K, int T, hipStream_t st) 
 }  // namespace
 
 namespace {
-// Q8_0 weights x Q8_0 activations, passes of up to 16 tokens. xq: row-SoA Q8_0 rows (quantize.hip) or null and x_f32 is quantized first. Its tables
+// Q8_0 / Q5_0 weights x Q8_0 activations, passes of up to 16 tokens. xq: row-SoA Q8_0 rows (quantize.hip) or null and x_f32 is quantized first. Its tables
 // (operand-ordered values + f32 scales of both 32-slot halves, then a quantized copy of 64 f32 rows) are written by a prologue launch per call.
 Scr * scratch80(int dev, hipStream_t st, size_t need) {
     std::lock_guard<std::mutex> lk(g_scr_mu);
@@ -720,7 +782,7 @@ Scr * scratch80(int dev, hipStream_t st, size_t need) {
 size_t q80_need(int K) { return 2 * ((size_t) (K / 32) * 1024 + (size_t) (K / 32) * 128) + (size_t) 64 * pm_q80_row_bytes(K) + 512; }
 
 // reuse_prep: the tables of this (device, stream) already describe these activations (pm_launch_silu_mul_q80_tab wrote them): no quantizer, no prologue launch
-int launch_q80(const void * W, const void * xq, const float * x_f32, float * Y, int K, int N, int T, const float * bias, const float * resid, int reuse_prep, hipStream_t st) {
+int launch_q80(int type, const void * W, const void * xq, const float * x_f32, float * Y, int K, int N, int T, const float * bias, const float * resid, int reuse_prep, hipStream_t st) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
     const int nb = K / 32;
@@ -741,14 +803,14 @@ int launch_q80(const void * W, const void * xq, const float * x_f32, float * Y, 
     const int cus = pm_device_cus();
     const int grid = N / 32 >= cus ? cus : (N + 31) / 32;
     const int rows = (N + grid - 1) / grid, nrg = (rows + 31) / 32;
-    const size_t lds = pm_mmq_i8_lds_bytes(PM_Q8_0, K);
+    const size_t lds = pm_mmq_i8_lds_bytes(type, K);
     constexpr int tmax = 16;                         // (the 32-token form spills 236 B: 502 vs 422 us per Qwen2.5-72B layer at 32 tokens - two passes of 16 it is)
     for (int t0 = 0; t0 < T; t0 += tmax) {
         const int tn = T - t0 < tmax ? T - t0 : tmax;
         uint8_t * tab = base + (t0 / 32) * (qtab + dtab);
         MmqP p = {};
         p.t_off = t0 % 32;
-        p.W = (const uint8_t *) W; p.row_stride = (long) pm_weight_row_stride(PM_Q8_0, K); p.N = N; p.K = K; p.T = tn;
+        p.W = (const uint8_t *) W; p.row_stride = (long) pm_weight_row_stride(type, K); p.N = N; p.K = K; p.T = tn;
         p.qT = tab; p.bsT = tab + qtab;                            // (bsT: here the f32 activation scales [blk][32])
         p.y = Y + (size_t) t0 * N; p.y_stride = N; p.bias = bias; p.resid = resid ? resid + (size_t) t0 * N : nullptr;
         p.rgb_log2 = rgb_log2_for(nrg);
@@ -756,7 +818,8 @@ int launch_q80(const void * W, const void * xq, const float * x_f32, float * Y, 
             pm_allow_big_lds((const void *) kern, 150 * 1024);
             hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, p);
         };
-        if (tn <= 8) go(mmq_i8_kernel<PM_Q8_0, 4>); else go(mmq_i8_kernel<PM_Q8_0, 8>);
+        if (type == PM_Q5_0) { if (tn <= 8) go(mmq_i8_kernel<PM_Q5_0, 4>); else go(mmq_i8_kernel<PM_Q5_0, 8>); }
+        else                 { if (tn <= 8) go(mmq_i8_kernel<PM_Q8_0, 4>); else go(mmq_i8_kernel<PM_Q8_0, 8>); }
     }
     return 0;
 }
@@ -804,7 +867,7 @@ int pm_launch_mmq_i8(int type, const void * W, const void * xq, const float * x_
                      const float * bias, const float * resid, int reuse_prep, hipStream_t st) {
     const int rc = pm_mmq_i8_check(type, K, N, T);
     if (rc) return rc;
-    if (type == PM_Q8_0) return launch_q80(W, xq, x_f32, Y, K, N, T, bias, resid, reuse_prep, st);
+    if (pm_q80_family(type)) return launch_q80(type, W, xq, x_f32, Y, K, N, T, bias, resid, reuse_prep, st);
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
     const int nsb = K / 256;

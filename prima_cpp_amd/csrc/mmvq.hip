@@ -2,7 +2,7 @@
 //
 // Replaces, for tensors in our buffers, the reference's
 //   ggml_compute_forward_mul_mat (ggml/src/ggml.c:12377) -> ggml_vec_dot_q4_K_q8_K (ggml-quants.c:7713),
-//   ggml_vec_dot_q5_K_q8_K (:8281), ggml_vec_dot_q6_K_q8_K (:8918), ggml_vec_dot_q8_0_q8_0 (:5518),
+//   ggml_vec_dot_q5_K_q8_K (:8281), ggml_vec_dot_q6_K_q8_K (:8918), ggml_vec_dot_q8_0_q8_0 (:5518), ggml_vec_dot_q5_0_q8_0 (:4789),
 // and, fused into its prologue, the activation side of that function: quantize_row_q8_K (ggml-quants.c:3785) /
 // quantize_row_q8_0 (:848) preceded, when asked, by ggml_compute_forward_rms_norm_f32 (ggml.c:11950) * weight.
 // Integer arithmetic is identical to the reference (int8 x int4/5/6/8 products, int32 sums, 6-bit scales/mins,
@@ -132,7 +132,7 @@ int launch_types(const GemvP & p_in, bool pair, int grid, size_t lds, bool dbg, 
 
 int nv_of(int type) { return type == PM_Q4_K ? QT<PM_Q4_K>::NV : type == PM_Q6_K ? 64 : 32; }
 
-bool type_ok(int t) { return t == PM_Q4_K || t == PM_Q5_K || t == PM_Q6_K || t == PM_Q8_0; }
+bool type_ok(int t) { return t == PM_Q4_K || t == PM_Q5_K || t == PM_Q6_K || t == PM_Q8_0 || t == PM_Q5_0; }
 
 } // namespace
 
@@ -150,6 +150,7 @@ size_t pm_weight_row_bytes(int type, int64_t K) {
         case PM_F32:  return (size_t) K * 4;
         case PM_F16:  return (size_t) K * 2;
         case PM_Q8_0: return (size_t) (K / 32) * PM_BS_Q8_0;
+        case PM_Q5_0: return (size_t) (K / 32) * PM_BS_Q5_0;
         case PM_Q4_K: return (size_t) (K / 256) * PM_BS_Q4_K;
         case PM_Q5_K: return (size_t) (K / 256) * PM_BS_Q5_K;
         case PM_Q6_K: return (size_t) (K / 256) * PM_BS_Q6_K;
@@ -160,13 +161,14 @@ size_t pm_weight_row_bytes(int type, int64_t K) {
 size_t pm_weight_row_stride(int type, int64_t K) {
     switch (type) {
         case PM_Q8_0: { const size_t nb = K / 32;  return nb * 32 + ((nb * 2 + 15) & ~(size_t) 15); }
+        case PM_Q5_0: return pm_q50_row_stride((size_t) (K / 32));
         case PM_Q6_K: return pm_q6k_row_stride((size_t) (K / 256));
     }
     return pm_weight_row_bytes(type, K);
 }
 
 // Validates a fused job list and fills the kernel argument block. ta <= tb are the (at most two) quant types in the
-// canonical order of the instantiated kernels: (Q4_K,Q4_K) (Q5_K,Q5_K) (Q6_K,Q6_K) (Q8_0,Q8_0) (Q4_K,Q6_K) (Q4_K,Q5_K); job 0 is
+// canonical order of the instantiated kernels: (Q4_K,Q4_K) (Q5_K,Q5_K) (Q6_K,Q6_K) (Q8_0,Q8_0) (Q5_0,Q5_0) (Q4_K,Q6_K) (Q4_K,Q5_K); job 0 is
 // always a `ta` job (the kernel pre-issues it). grid_fixed > 0: the caller's grid (attn_wo.hip), else chosen here.
 int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_out, int & tb_out, bool & pair_out, size_t & lds_out, int & grid_out) {
     if (a.njobs < 1 || a.njobs > 3) return -4;
@@ -184,10 +186,11 @@ int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_
         if (t != ta) { if (tb == ta) tb = t; else if (t != tb) return -1; }
         if ((a.job[j].W2 != nullptr) != pair) return -1;
     }
-    // a Q8_0 job needs Q8_0-quantized activations, the K-quants need Q8_K: one prologue serves only one family
-    if ((ta == PM_Q8_0) != (tb == PM_Q8_0)) return -1;
-    if (ta == PM_Q8_0 ? a.K % 32 : a.K % 256) return -2;
+    // Q8_0 / Q5_0 jobs need Q8_0-quantized activations, the K-quants need Q8_K: one prologue serves only one family
+    if (pm_q80_family(ta) != pm_q80_family(tb)) return -1;
+    if (pm_q80_family(ta) ? a.K % 32 : a.K % 256) return -2;
     if (pair && ta != tb) return -1;
+    if (pm_q80_family(ta) && ta != tb) return -1;                    // (Q5_0 next to Q8_0 in one launch: not instantiated)
     if (ta != tb) {
         if (ta != PM_Q4_K) { const int t = ta; ta = tb; tb = t; }     // canonical order: Q4_K first
         if (ta != PM_Q4_K || (tb != PM_Q6_K && tb != PM_Q5_K)) return -1;
@@ -246,7 +249,7 @@ int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_
     }
     if (p.job[0].is_b)                                // the kernel pre-issues job 0 with the TA code path: put a TA job first
         for (int j = 1; j < 3; ++j) if (p.job[j].N > 0 && !p.job[j].is_b) { const GemvJob t = p.job[0]; p.job[0] = p.job[j]; p.job[j] = t; break; }
-    const int ablk = ta == PM_Q8_0 ? 32 : 256;
+    const int ablk = pm_q80_family(ta) ? 32 : 256;
     size_t lds = (size_t) ((a.K + 15) & ~15) + (size_t) (a.K / 16) * 4 + (size_t) ((a.K / ablk + 3) & ~3) * 4 + (size_t) rows_cap * 4;
     if (att_lds > lds) lds = att_lds;
     if (lds > 150 * 1024) return -4;
@@ -278,6 +281,7 @@ int pm_launch_gemv_fused(const pm_gemv_fused & a, hipStream_t st) {
     if (ta == PM_Q5_K && tb == PM_Q5_K) PM_L(PM_Q5_K, PM_Q5_K);
     if (ta == PM_Q6_K && tb == PM_Q6_K) PM_L(PM_Q6_K, PM_Q6_K);
     if (ta == PM_Q8_0 && tb == PM_Q8_0) PM_L(PM_Q8_0, PM_Q8_0);
+    if (ta == PM_Q5_0 && tb == PM_Q5_0) PM_L(PM_Q5_0, PM_Q5_0);
     if (ta == PM_Q4_K && tb == PM_Q6_K) PM_L(PM_Q4_K, PM_Q6_K);
     if (ta == PM_Q4_K && tb == PM_Q5_K) PM_L(PM_Q4_K, PM_Q5_K);
 #undef PM_L
@@ -287,7 +291,7 @@ int pm_launch_gemv_fused(const pm_gemv_fused & a, hipStream_t st) {
 // Single-matrix entry with ncols pre-quantized activation columns: groups of 8 / 4 / 2 columns share one pass over the
 // weights (gemv_q_cols_kernel), a remaining single column - and pair / debug launches - go one launch per column.
 int pm_launch_gemv(const pm_gemv_args & a, hipStream_t st) {
-    const size_t xrow = a.type == PM_Q8_0 ? pm_q80_row_bytes(a.K) : pm_q8k_row_bytes(a.K);
+    const size_t xrow = pm_q80_family(a.type) ? pm_q80_row_bytes(a.K) : pm_q8k_row_bytes(a.K);
     int c = 0;
     while (c < a.ncols) {
         pm_gemv_fused f = {};
@@ -304,7 +308,7 @@ int pm_launch_gemv(const pm_gemv_args & a, hipStream_t st) {
             int rc = gemv_fill(f, 0, p, ta, tb, pr, lds1, grid);
             if (rc) return rc;
             // LDS: nc activation columns + nc results per row
-            const int ablk = ta == PM_Q8_0 ? 32 : 256;
+            const int ablk = pm_q80_family(ta) ? 32 : 256;
             const size_t col = (size_t) ((a.K + 15) & ~15) + (size_t) (a.K / 16) * 4 + (size_t) ((a.K / ablk + 3) & ~3) * 4;
             const size_t rows = (size_t) ((a.N + grid - 1) / grid + 4);
             while (nc > 1 && nc * col + rows * nc * 4 > 150 * 1024) nc /= 2;

@@ -54,6 +54,7 @@ int pm_launch_gemv_cols(int type, const GemvP & p, int nc, bool pair, int grid, 
         case PM_Q5_K: return launch_cols<PM_Q5_K>(p, nc, pair, grid, lds, st);
         case PM_Q6_K: return launch_cols<PM_Q6_K>(p, nc, pair, grid, lds, st);
         case PM_Q8_0: return launch_cols<PM_Q8_0>(p, nc, pair, grid, lds, st);
+        case PM_Q5_0: return launch_cols<PM_Q5_0>(p, nc, pair, grid, lds, st);
     }
     return -1;
 }

@@ -201,6 +201,38 @@ template <> struct QT<PM_Q8_0> {
     }
 };
 
+// ---------------------------------------------------------------- Q5_0 (row-SoA) --------------------
+// row: qs[nb32][16] | qh[nb32][4] | d[nb32] (pm355_device.h pm_q50_*); activations quantized to Q8_0 (vec_dot_type of Q5_0).   unit = one 32-block
+// Weight j of a block is ((qs[j % 16] >> 4 (j / 16)) & 0xF | qh bit j << 4) - 16 (dequantize_row_q5_0, ggml-quants.c:1563). The unsigned 5-bit
+// values 0..31 go into v_dot4 as they are and the -16 comes off with the activation's 16-value group sums (xs_gs): the same exact int32 per block
+// as ggml_vec_dot_q5_0_q8_0 (ggml-quants.c:4789), one scale multiply-add with d_w * d_a.
+__device__ __forceinline__ uint32_t q50_hbits(uint32_t qh, int sh) {      // bits sh .. sh + 3 of qh -> bit 4 of bytes 0 .. 3
+    return (((qh >> sh) & 0xFu) * 0x00204081u & 0x01010101u) << 4;
+}
+template <> struct QT<PM_Q5_0> {
+    static constexpr int NV = 32, LPB = 1, ABLK = 32;
+    typedef XT<NV> X;
+    struct Wr { u32x4 q; uint32_t h; uint16_t d; };
+    static __device__ __forceinline__ int group_base(int u, int g) { return u * 32 + 16 * g; }
+    static __device__ __forceinline__ void issue(Wr & w, const uint8_t * row, int K, int u) {
+        const uint32_t nb = (uint32_t) K / 32u;
+        w.q = ld_nt16(row + (uint32_t) u * 16u);
+        w.h = ld_nt4(row + pm_q50_qh_off(nb) + (uint32_t) u * 4u);
+        w.d = ld_nt2(row + pm_q50_d_off(nb) + (uint32_t) u * 2u);
+    }
+    static __device__ __forceinline__ float consume(const Wr & w, const X & x, int, float acc, int & isum, int & msum) {
+        int s = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            s = dot4((w.q[i] & 0x0F0F0F0Fu) | q50_hbits(w.h, 4 * i), x.q[i], s);
+            s = dot4(((w.q[i] >> 4) & 0x0F0F0F0Fu) | q50_hbits(w.h, 16 + 4 * i), x.q[4 + i], s);
+        }
+        s -= 16 * (x.gs[0] + x.gs[1]);
+        isum = s; msum = 0;
+        return fmaf((float) s, h2f(w.d) * x.yd, acc);
+    }
+};
+
 __device__ __forceinline__ float silu_f(float g) { return g / (1.0f + expf(-g)); }
 
 #ifndef PM_GEMV_BLOCK

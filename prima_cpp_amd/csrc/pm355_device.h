@@ -5,6 +5,7 @@
 //   Q5_K 176 B / 256 w : half d | half dmin | u8 scales[12] | u8 qh[32] | u8 qs[128]   (native)
 //   Q6_K 210 B / 256 w : u8 ql[128] | u8 qh[64] | i8 scales[16] | half d         (row-SoA in HBM, see repack.hip)
 //   Q8_0  34 B /  32 w : half d | i8 qs[32]                                      (row-SoA in HBM)
+//   Q5_0  22 B /  32 w : half d | u8 qh[4] | u8 qs[16]                           (row-SoA in HBM)
 //   Q8_K 292 B / 256 a : float d | i8 qs[256] | i16 bsums[16]                    (activations, native)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,8 +15,9 @@
 #define PM_QK_K 256
 #define PM_WAVE 64
 
-enum pm_type : int { PM_F32 = 0, PM_F16 = 1, PM_Q8_0 = 8, PM_Q4_K = 12, PM_Q5_K = 13, PM_Q6_K = 14, PM_Q8_K = 15 };
+enum pm_type : int { PM_F32 = 0, PM_F16 = 1, PM_Q5_0 = 6, PM_Q8_0 = 8, PM_Q4_K = 12, PM_Q5_K = 13, PM_Q6_K = 14, PM_Q8_K = 15 };
 
+#define PM_BS_Q5_0 22
 #define PM_BS_Q8_0 34
 #define PM_BS_Q4_K 144
 #define PM_BS_Q5_K 176
@@ -38,6 +40,12 @@ __host__ __device__ inline uint32_t pm_q6k_d_off(uint32_t nb, uint32_t b) {
     return PM_Q6K_SCD ? nb * 192u + (b >> 3) * 144u + cnt * 16u + (b & 7u) * 2u : nb * 208u + b * 2u;
 }
 __host__ __device__ inline size_t pm_q6k_row_stride(size_t nb) { return (nb * 210 + 15) & ~(size_t) 15; }
+// Q5_0 row-SoA (repack.hip), nb = K / 32 blocks: qs[nb][16] | qh[nb][4] | d[nb], the qh and d streams each padded to 16 bytes
+__host__ __device__ inline uint32_t pm_q50_qh_off(uint32_t nb) { return nb * 16u; }
+__host__ __device__ inline uint32_t pm_q50_d_off(uint32_t nb) { return nb * 16u + ((nb * 4u + 15u) & ~15u); }
+__host__ __device__ inline size_t pm_q50_row_stride(size_t nb) { return nb * 16 + ((nb * 4 + 15) & ~(size_t) 15) + ((nb * 2 + 15) & ~(size_t) 15); }
+// weights whose vec_dot_type is Q8_0 (32-value activation blocks, ggml.c type_traits): one activation family in every kernel
+__host__ __device__ constexpr bool pm_q80_family(int t) { return t == PM_Q8_0 || t == PM_Q5_0; }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));

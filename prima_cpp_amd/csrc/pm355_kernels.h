@@ -34,12 +34,12 @@ static inline size_t pm_q80_row_bytes(int K) { return (size_t) K + (size_t) (K /
 // bytes of one WEIGHT row in GGUF order (== ggml_row_size)
 size_t pm_weight_row_bytes(int type, int64_t K);
 // row STRIDE in HBM: == row bytes except that the trailing fp16 scale stream of the row-SoA layouts
-// (Q6_K, Q8_0) is padded to 16 B so every row (and every field stream) starts 16-B aligned for any K
+// (Q6_K, Q8_0, Q5_0) is padded to 16 B so every row (and every field stream) starts 16-B aligned for any K
 size_t pm_weight_row_stride(int type, int64_t K);
 int pm_gemv_units_per_row(int type, int64_t K);
   // units of the mat-vec's per-(row, unit) debug partials
-// HBM layout != GGUF block order (repack.hip): Q4_K (12), Q6_K (14), Q8_0 (8)
-static inline bool pm_type_is_repacked(int type) { return type == 12 || type == 14 || type == 8; }
+// HBM layout != GGUF block order (repack.hip): Q4_K (12), Q6_K (14), Q8_0 (8), Q5_0 (6)
+static inline bool pm_type_is_repacked(int type) { return type == 12 || type == 14 || type == 8 || type == 6; }
 
 // optional second output of the Q8_K quantizers: the activation tables of the small-batch mat-mul (mmq_i8.hip: per 32-row pass, the F16
 // 16-value sums in MFMA operand order | the transposed block scales) - that mat-mul then needs no prologue launch. base == null: off
@@ -57,14 +57,14 @@ void pm_launch_silu_mul_q8k(const float * gate, const float * up, void * y, int 
 void pm_launch_rmsnorm_q8k(const float * x, const float * w, float * ynorm, void * yq, int K, int rows, float eps, hipStream_t st, void * ynorm_f16 = nullptr,
                            pm_q8k_tables tab = {});
 
-// weight repack (row-local, bijective):  GGUF block order <-> HBM row-SoA (Q4_K, Q6_K, Q8_0); identity for the rest
+// weight repack (row-local, bijective):  GGUF block order <-> HBM row-SoA (Q4_K, Q6_K, Q8_0, Q5_0); identity for the rest
 void pm_launch_repack(int type, const void * src, void * dst, int64_t K, int64_t nrows, int to_device_layout, hipStream_t st);
 
 // y[N] = W[N,K] . xq (+bias)(+resid);  optional second matrix W2 (same type/shape): y = silu(W.x) * (W2.x)
 struct pm_gemv_args {
     int type; int K; int N;
     const void * W; const void * W2;
-    const void * xq;            // quantized activation row(s) (Q8_K row-SoA, or Q8_0 row-SoA for Q8_0 weights)
+    const void * xq;            // quantized activation row(s) (Q8_K row-SoA, or Q8_0 row-SoA for Q8_0 / Q5_0 weights)
     int ncols;                  // 1..8 activation columns (rows of xq, stride = row bytes)
     float * y; size_t y_stride; // y[col * y_stride + n]
     const float * bias;         // [N] or null

@@ -16,6 +16,8 @@
 //                                   rounds 1-4 and -DPM_Q6K_SCD=0: scales[nb][16] | d[nb])
 //                                   unit (b, hh, v): ql[64hh+16v, +16) | ql[64hh+32+16v, +16) | qh[32hh+16v, +16)
 //   Q8_0 row (nb blocks, U = nb)  : qa[U][16] | qb[U][16] | d[nb]
+//   Q5_0 row (nb blocks, U = nb)  : qs[U][16] | qh[U][4] (padded to 16 B) | d[nb] (padded to 16 B)    unit = one 32-block: its 16 nibble bytes,
+//                                   4 high-bit bytes and fp16 d are three aligned loads (pm355_device.h pm_q50_*; 22-B native blocks are not 16-B aligned)
 // Q5_K (176 = 11x16 B) stays native (identity): it only serves attn_v of the 70B mixture (2 % of the bytes).
 // to_device = 1: GGUF order -> HBM order (used by set_tensor / the weight loader);
 // to_device = 0: inverse (get_tensor). Pure byte permutation; tests check round trips bit-exactly.
@@ -42,6 +44,11 @@ __global__ __launch_bounds__(256) void repack_kernel(const uint16_t * __restrict
         const long b = o / PM_BS_Q4_K, f = o - b * PM_BS_Q4_K;
         if (f < 16) so = nb * 128 + b * 16 + f;                       // header: d, dmin, scales[12]
         else { const long q = f - 16, j = q >> 5, r = q & 31; so = (r >> 4) * nb * 64 + (4 * b + j) * 16 + (r & 15); }
+    } else if (type == PM_Q5_0) {                                     // block: d[2] | qh[4] | qs[16]
+        const long b = o / PM_BS_Q5_0, f = o - b * PM_BS_Q5_0;
+        if (f < 2)      so = pm_q50_d_off((uint32_t) nb) + b * 2;
+        else if (f < 6) so = pm_q50_qh_off((uint32_t) nb) + b * 4 + (f - 2);
+        else            so = b * 16 + (f - 6);
     } else {                                                          // PM_Q8_0
         const long b = o / PM_BS_Q8_0, f = o - b * PM_BS_Q8_0;
         if (f < 2) so = nb * 32 + b * 2;
@@ -58,7 +65,7 @@ void pm_launch_repack(int type, const void * src, void * dst, int64_t K, int64_t
         if (src != dst) hipMemcpyAsync(dst, src, rb * nrows, hipMemcpyDeviceToDevice, st);
         return;
     }
-    const long nb = type == PM_Q8_0 ? K / 32 : K / 256;
+    const long nb = pm_q80_family(type) ? K / 32 : K / 256;
     const long halfs = (long) rb / 2;
     const long n = halfs * nrows;
     hipLaunchKernelGGL(repack_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st,

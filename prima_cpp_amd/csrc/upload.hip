@@ -113,7 +113,7 @@ void pm355_uploader_free(pm355_uploader * u) {
 }
 
 // host (pageable or pinned) GGUF-order bytes -> device. type < 0 or a type whose HBM layout is the GGUF layout: plain bytes;
-// row-SoA types (Q4_K/Q6_K/Q8_0 matrices): `nbytes` must be whole rows of K weights, dev = first destination row in the HBM layout.
+// row-SoA types (Q4_K/Q6_K/Q8_0/Q5_0 matrices): `nbytes` must be whole rows of K weights, dev = first destination row in the HBM layout.
 // Returns after the last chunk is ENQUEUED (host memory may be reused / unmapped: every byte has been copied into the pinned ring).
 int pm355_upload(pm355_uploader * u, int type, int64_t K, const void * host, void * dev, size_t nbytes, int repack) {
     if (!u || !host || !dev) return PM355_E_SHAPE;

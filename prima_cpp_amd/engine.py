@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .lib import F32, Q4_K, Q5_K, Q6_K, Q8_0, check, ptr, stream_ptr  # noqa: F401
+from .lib import F32, Q4_K, Q5_0, Q5_K, Q6_K, Q8_0, check, ptr, stream_ptr  # noqa: F401
 
 (T_ATTN_NORM, T_WQ, T_WK, T_WV, T_WO, T_FFN_NORM, T_FFN_GATE, T_FFN_UP, T_FFN_DOWN, T_BQ, T_BK, T_BV,
  T_TOK_EMBD, T_OUT_NORM, T_OUTPUT, T_ROPE_FREQS) = range(16)
@@ -33,13 +33,20 @@ QWEN25_72B = dict(arch=1, n_layer=80, n_embd=8192, n_head=64, n_head_kv=8, head_
 
 
 def q4_k_m_types(hp, il):
-    """The Q4_K_M mixture of llama_tensor_get_type (src/llama.cpp:19271-19490) for layer il."""
+    """The Q4_K_M mixture of llama_tensor_get_type (src/llama.cpp:19271-19490) for layer il, with the reference's fallback for rows that are
+    no multiple of 256 (:19516-19548: Q4_K -> Q5_0, Q6_K -> Q8_0; Qwen2.5-72B's ffn_down, K = n_ff = 29568)."""
     n = hp["n_layer"]
     more = il < n // 8 or il >= 7 * n // 8 or (il - n // 8) % 3 == 2       # use_more_bits (:19260)
     is70 = n == 80 and hp["n_head"] // hp["n_head_kv"] == 8                 # MODEL_70B heuristic (:19382)
     v = Q6_K if more else (Q5_K if is70 else Q4_K)
-    return {T_WQ: Q4_K, T_WK: Q4_K, T_WV: v, T_WO: Q4_K, T_FFN_GATE: Q4_K, T_FFN_UP: Q4_K,
-            T_FFN_DOWN: Q6_K if more else Q4_K}
+
+    from .gguf import fallback_type
+
+    def fb(t, k):
+        return fallback_type(t, k, "reference")             # (Q5_K -> Q5_1 is not served: ValueError)
+    E, F = hp["n_embd"], hp["n_ff"]
+    return {T_WQ: fb(Q4_K, E), T_WK: fb(Q4_K, E), T_WV: fb(v, E), T_WO: fb(Q4_K, E), T_FFN_GATE: fb(Q4_K, E), T_FFN_UP: fb(Q4_K, E),
+            T_FFN_DOWN: fb(Q6_K if more else Q4_K, F)}
 
 
 def q6_k_types(hp, il):

@@ -22,8 +22,8 @@ _SCALAR = {T_U8: "<B", T_I8: "<b", T_U16: "<H", T_I16: "<h", T_U32: "<I", T_I32:
            T_U64: "<Q", T_I64: "<q", T_F64: "<d"}
 
 # ggml types on the path: (block elements, block bytes)   (ggml/src/ggml-common.h)
-F32, F16, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 8, 12, 13, 14
-BLOCK = {F32: (1, 4), F16: (1, 2), Q8_0: (32, 34), Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210)}
+F32, F16, Q5_0, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 6, 8, 12, 13, 14
+BLOCK = {F32: (1, 4), F16: (1, 2), Q5_0: (32, 22), Q8_0: (32, 34), Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210)}
 
 
 def row_size(t, k):
@@ -203,6 +203,22 @@ def q4_k_m_type(kind, il, n_layer, is_70b=False):
     return Q4_K
 
 
+# what llama_tensor_get_type writes instead of a K-quant whose rows are no multiple of 256 (src/llama.cpp:19516-19548); Q5_K -> Q5_1 is not served here
+REFERENCE_FALLBACK = {Q4_K: Q5_0, Q6_K: Q8_0}
+
+
+def fallback_type(t, k, fallback="q8_0"):
+    """The type a matrix of rows of k weights gets when the mixture asks for `t`. fallback="q8_0": every K-quant -> Q8_0 (this project's
+    fixtures before Q5_0 was served); "reference": the reference's table, Q4_K -> Q5_0, Q6_K -> Q8_0."""
+    if t not in (Q4_K, Q5_K, Q6_K) or k % 256 == 0:
+        return t
+    if fallback == "q8_0":
+        return Q8_0
+    if fallback == "reference" and t in REFERENCE_FALLBACK:
+        return REFERENCE_FALLBACK[t]
+    raise ValueError(f"no fallback for type {t} at K = {k} ({fallback})")
+
+
 def _cyclic(pool, off, n):
     """n bytes of `pool` read cyclically from offset off (slice copies: memcpy speed; np.tile on a 1-D array is ~50x slower)."""
     out = np.empty(n, dtype=np.uint8)
@@ -243,6 +259,8 @@ def random_valid_blocks(t, nrows, k, rng, scale=None):
     u = rng.uniform(0.5, 1.5, nb)
     if t == Q8_0:
         raw[:, 0:2] = f16(u * scale / 64.0)
+    elif t == Q5_0:                                       # q - 16 in [-16, 15]
+        raw[:, 0:2] = f16(u * scale / 8.0)
     elif t in (Q4_K, Q5_K):
         qmax = 15 if t == Q4_K else 31
         d = u * scale / (qmax * 16.0)
@@ -256,11 +274,13 @@ def random_valid_blocks(t, nrows, k, rng, scale=None):
 
 
 def write_synthetic_model(path, arch, n_layer, n_embd, n_head, n_head_kv, n_ff, n_vocab, n_ctx_train=8192, seed=1234,
-                          rope_freqs=None, is_70b=False, all_type=None, distinct_layers=2, branch_scale=1.0):
+                          rope_freqs=None, is_70b=False, all_type=None, distinct_layers=2, branch_scale=1.0, fallback="q8_0"):
     """A Llama / Qwen2-shaped GGUF with random valid quant blocks in the Q4_K_M mixture (or every matrix `all_type`).
     To bound generation time for multi-GB shapes only `distinct_layers` different random tensors are drawn per
     (tensor kind, type); further layers reuse them rolled by a layer-dependent number of rows.
     branch_scale multiplies the weights of the two projections that write into the residual stream (attn_output, ffn_down).
+    fallback: the type of a K-quant matrix whose rows are no multiple of 256 - "q8_0" (always Q8_0) or "reference" (Q4_K -> Q5_0,
+    Q6_K -> Q8_0: what the reference's quantizer writes, e.g. ffn_down of a Qwen2.5-72B Q4_K_M file); see fallback_type.
     (It does NOT tame the logit-level spread between two float summation orders: that spread comes from the int8 re-quantization
     of the activations in front of every mat-vec, which turns a perturbation eps into flips of size `step` with probability
     eps/step, i.e. amplitude ~sqrt(eps*step) per stage, and saturates at ~step after a handful of stages - DESIGN.md, parity.)"""
@@ -278,8 +298,7 @@ def write_synthetic_model(path, arch, n_layer, n_embd, n_head, n_head_kv, n_ff, 
     def mat(kind, t, K, N, il, n_out=None):
         """-> (type, writer(file)): rows of the pooled tensor rolled by a layer-dependent amount (tiled up to n_out rows),
         written straight to the file so multi-GB models never sit in memory."""
-        if t in (Q4_K, Q5_K, Q6_K) and K % 256:
-            t = Q8_0                                     # llama_tensor_get_type fallback for K % 256 != 0 (src/llama.cpp:19547)
+        t = fallback_type(t, K, fallback)                # llama_tensor_get_type fallback for K % 256 != 0 (src/llama.cpp:19516-19548)
         key = (kind, t, il % distinct_layers)
         if key not in pool:
             pool[key] = random_valid_blocks(t, N, K, rng, scale=(branch_scale if kind in ("wo", "ffn_down") else 1.0) / np.sqrt(K))

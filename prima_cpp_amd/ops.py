@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .lib import F16, F32, Q4_K, Q5_K, Q6_K, Q8_0, Q8_K, check, ptr, stream_ptr  # noqa: F401
+from .lib import F16, F32, Q4_K, Q5_0, Q5_K, Q6_K, Q8_0, Q8_K, check, ptr, stream_ptr  # noqa: F401
 
 
 def _dev():
@@ -34,7 +34,7 @@ def upload_weight(qtype, blocks, K, N):
     blocks = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
     assert blocks.size == L.row_size(qtype, K) * N, (blocks.size, L.row_size(qtype, K) * N)
     raw = torch.from_numpy(blocks).to(_dev())
-    if qtype in (Q4_K, Q6_K, Q8_0):
+    if qtype in (Q4_K, Q6_K, Q8_0, Q5_0):
         dst = torch.zeros(N * lib.pm355_row_stride(qtype, K), dtype=torch.uint8, device=raw.device)
         check(lib.pm355_repack_rows(qtype, ptr(raw), ptr(dst), K, N, 1, stream_ptr()), "repack_rows")
         return QWeight(qtype, K, N, dst)
@@ -44,7 +44,7 @@ def upload_weight(qtype, blocks, K, N):
 def download_weight(w):
     """ggml_backend_tensor_get semantics: HBM layout -> host GGUF-order bytes."""
     lib = L.load()
-    if w.type in (Q4_K, Q6_K, Q8_0):
+    if w.type in (Q4_K, Q6_K, Q8_0, Q5_0):
         tmp = torch.empty(w.N * L.row_size(w.type, w.K), dtype=torch.uint8, device=w.data.device)
         check(lib.pm355_repack_rows(w.type, ptr(w.data), ptr(tmp), w.K, w.N, 0, stream_ptr()), "repack_rows")
         return tmp.cpu().numpy()
@@ -84,7 +84,7 @@ def rms_norm(x, w, eps, want_f32=True, want_q8=False):
 
 
 def vec_dot_act_type(qtype):
-    return Q8_0 if qtype == Q8_0 else Q8_K
+    return Q8_0 if qtype in (Q8_0, Q5_0) else Q8_K
 
 
 def mul_mat_vec(w, x=None, xq=None, w2=None, bias=None, resid=None, ncols=1):
