@@ -218,7 +218,7 @@ void pm_launch_fill_random_blocks(int type, void * dst, int64_t K, int64_t nrows
     if (type == PM_F32) { hipLaunchKernelGGL(fill_random_f32_kernel, dim3((unsigned) ((n / 4 + 255) / 256)), dim3(256), 0, st, (float *) dst, n / 4, seed, 0.0f, scale); return; }
     if (type == PM_F16) { hipLaunchKernelGGL(fill_random_f16_kernel, dim3((unsigned) ((n / 2 + 255) / 256)), dim3(256), 0, st, (uint16_t *) dst, n / 2, seed, scale); return; }
     const long nd = (n + 3) / 4;
-    const long nb_row = pm_q80_family(type) ? K / 32 : K / 256;
+    const long nb_row = K / pm_block_len(type);
     hipLaunchKernelGGL(fill_random_blocks_kernel, dim3((unsigned) ((nd + 255) / 256)), dim3(256), 0, st, type, (uint32_t *) dst, nd, nb_row * nrows, nb_row, seed, scale);
     hipLaunchKernelGGL(fix_scales_kernel, dim3((unsigned) ((nb_row * nrows + 255) / 256)), dim3(256), 0, st, type, (uint8_t *) dst, nb_row * nrows, nb_row, (long) rb, seed, scale);
 }
@@ -765,7 +765,7 @@ int small_ffn(pm355_model * m, const Layer & L, int T, bool small, const float *
     bool prepped = false, gu_done = false;
     // 2 tokens: the pair mat-vec with two column slots - one pass over both matrices, silu(gate) * up in its epilogue (~50 us against 60 for the
     // two-matrix launch of the matrix-core kernel + the product launch)
-    const bool pair_cols = T == 2 && (wg.type == PM_Q4_K || wg.type == PM_Q6_K);
+    const bool pair_cols = T == 2 && pm_gemv_col_slots(wg.type, true, T) == 2;
     if (!pair_cols && small && m->h2 && pm_mmq_i8_check(wg.type, (int) wg.K, (int) wg.N, T) == 0) {
         // gate and up: one weight pass each for all tokens, then silu(gate) * up (the pair mat-vec would take one launch per token)
         float * ys[2] = {m->h, m->h2}; const float * bs[2] = {nullptr, nullptr};

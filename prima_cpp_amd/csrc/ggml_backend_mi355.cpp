@@ -52,7 +52,7 @@ int drepack(int type, const void * src, void * dst, int64_t K, int64_t rows, int
     return pm355_repack_rows(type, src, dst, K, rows, to_dev, st);
 }
 
-bool is_soa_type(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q5_0; }   // repack.hip
+bool is_soa_type(enum ggml_type t) { return pm_type_is_repacked((int) t); }   // repack.hip
 // ... of weight MATRICES. A 1-D quantized tensor - the quantized KV caches (ggml_new_tensor_1d(type_k, n_embd_k_gqa * kv_size),
 // llama_kv_cache_init src/llama.cpp:3548-3551) - keeps ggml's native block order, so the byte offsets of the reference's cache views
 // and of state save / restore stay valid (attn_q8.hip)
@@ -60,7 +60,7 @@ bool is_soa_tensor(const struct ggml_tensor * t) {
     const struct ggml_tensor * r = t->view_src ? t->view_src : t;
     return is_soa_type(r->type) && r->ne[1] > 1;
 }
-bool is_gemv_type(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q5_0; }
+bool is_gemv_type(enum ggml_type t) { return pm_is_quant_weight((int) t); }
 
 struct dev_ctx { int device; std::string name, desc; };
 struct buft_ctx { int device; std::string name; };
@@ -464,7 +464,7 @@ bool mul_mat_quant_ok(const struct ggml_tensor * op) {
     if (!ggml_is_contiguous(a) || !ggml_is_contiguous(b) || !ggml_is_contiguous(op)) return false;
     if (a->ne[2] != 1 || a->ne[3] != 1 || b->ne[2] != 1 || b->ne[3] != 1) return false;
     if (is_soa_type(a->type) && (a->view_src || !is_soa_tensor(a))) return false;   // row-SoA layout is per allocated weight matrix (not views, not the 1-D quantized KV caches)
-    if (a->ne[0] % (mi355::q80_act_type(a->type) ? 32 : 256)) return false;
+    if (a->ne[0] % pm_block_len((int) a->type)) return false;
     return a->ne[0] <= 131072;
 }
 
@@ -527,7 +527,7 @@ bool supports_op_impl(const struct ggml_tensor * op) {
         }
         case GGML_OP_GET_ROWS:
             return b->type == GGML_TYPE_I32 && ggml_is_contiguous(b) && b->ne[1] == 1 && b->ne[2] == 1 && b->ne[3] == 1 &&
-                   (a->type == GGML_TYPE_F32 || (is_gemv_type(a->type) && a->type != GGML_TYPE_Q5_0 /* (no Q5_0 embedding rows: layer_ops.hip) */ && ggml_is_contiguous(a) && a->ne[2] == 1 && a->ne[3] == 1 && !a->view_src && (!is_soa_type(a->type) || is_soa_tensor(a))));
+                   (a->type == GGML_TYPE_F32 || (is_gemv_type(a->type) && pm_embed_type_ok((int) a->type) /* (no Q5_0 embedding rows: layer_ops.hip) */ && ggml_is_contiguous(a) && a->ne[2] == 1 && a->ne[3] == 1 && !a->view_src && (!is_soa_type(a->type) || is_soa_tensor(a))));
         default:
             return false;
     }

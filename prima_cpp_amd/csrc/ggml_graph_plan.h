@@ -26,6 +26,7 @@
 #include "ggml.h"
 #include "ggml-backend.h"
 #include "../../include/prima_mi355.h"
+#include "pm355_types.h"
 
 #include <cstdint>
 #include <cstring>
@@ -102,10 +103,17 @@ struct ptr_count {
 inline bool is_view_op(enum ggml_op op) {
     return op == GGML_OP_NONE || op == GGML_OP_RESHAPE || op == GGML_OP_VIEW || op == GGML_OP_PERMUTE || op == GGML_OP_TRANSPOSE;
 }
-inline bool quant_matvec_type(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q5_0; }
-inline bool soa_type(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q5_0; }
-// weights whose vec_dot_type is Q8_0 (32-value blocks: K % 32)
-inline bool q80_act_type(enum ggml_type t) { return t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q5_0; }
+// a tensor's ggml_type goes into the C ABI and into the type table (pm355_types.h) as a plain int: the two enumerations must agree
+static_assert((int) GGML_TYPE_F32 == PM_F32, "ggml_type / pm_type");
+static_assert((int) GGML_TYPE_F16 == PM_F16, "ggml_type / pm_type");
+static_assert((int) GGML_TYPE_Q5_0 == PM_Q5_0, "ggml_type / pm_type");
+static_assert((int) GGML_TYPE_Q8_0 == PM_Q8_0, "ggml_type / pm_type");
+static_assert((int) GGML_TYPE_Q4_K == PM_Q4_K, "ggml_type / pm_type");
+static_assert((int) GGML_TYPE_Q5_K == PM_Q5_K, "ggml_type / pm_type");
+static_assert((int) GGML_TYPE_Q6_K == PM_Q6_K, "ggml_type / pm_type");
+static_assert((int) GGML_TYPE_Q8_K == PM_Q8_K, "ggml_type / pm_type");
+inline bool quant_matvec_type(enum ggml_type t) { return pm_is_quant_weight((int) t); }
+inline bool q80_act_type(enum ggml_type t) { return pm_q80_family((int) t); }        // weights whose vec_dot_type is Q8_0
 inline bool f32_vec(const ggml_tensor * t, int64_t n) {           // contiguous f32 [n, 1, 1, 1]
     return t && t->type == GGML_TYPE_F32 && t->ne[0] == n && t->ne[1] == 1 && t->ne[2] == 1 && t->ne[3] == 1 && t->nb[0] == 4;
 }
@@ -247,7 +255,7 @@ private:
         if (!t || t->op != GGML_OP_MUL_MAT) return false;
         const ggml_tensor * w = t->src[0], * x = t->src[1];
         if (!w || !x || !quant_matvec_type(w->type) || w->view_src || !ggml_is_contiguous(w) || w->ne[2] != 1 || w->ne[3] != 1) return false;
-        if (w->ne[0] % (q80_act_type(w->type) ? 32 : 256) || w->ne[0] > 131072) return false;
+        if (w->ne[0] % pm_block_len((int) w->type) || w->ne[0] > 131072) return false;
         if (!f32_vec(x, w->ne[0]) || !f32_vec(t, w->ne[1])) return false;
         return !x_expected || x == x_expected;
     }

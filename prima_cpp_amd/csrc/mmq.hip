@@ -17,6 +17,9 @@
 #include "pm355_kernels.h"
 #include <stdlib.h>
 
+// what pm_launch_gemm_q_h serves (through mmq_pf.hip where that takes the shape, else with the kernels of this file): every quantized weight type
+constexpr uint32_t GEMM_Q_TYPES = PM_QUANT_WEIGHTS;
+
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -603,7 +606,7 @@ int pm_launch_gemm_q_ex(int type, const void * W, const float * X, float * Y, in
 int pm_launch_gemm_q_h(int type, const void * W, const float * X, const void * x_f16, float * Y, void * y_f16, int K, int N, int T,
                        const float * bias, const float * resid, const float * silu_gate, int reuse_x, hipStream_t st) {
     if (K % 64 || (!pm_q80_family(type) && K % 256) || N % 4) return -2;
-    if (type != PM_Q4_K && type != PM_Q5_K && type != PM_Q6_K && type != PM_Q8_0 && type != PM_Q5_0) return -1;
+    if (!pm_in_set(GEMM_Q_TYPES, type)) return -1;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
     const size_t need = (size_t) T * K;

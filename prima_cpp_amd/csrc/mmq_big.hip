@@ -29,6 +29,9 @@
 #include "pm355_kernels.h"
 #include <mutex>
 
+// what pm_launch_mmq_big serves: instantiated for Q4_K and Q6_K only (BT<>, Stage<>); the other types take the F16 prompt kernels (mmq_pf.hip, mmq.hip)
+constexpr uint32_t MMQ_BIG_TYPES = pm_type_set(PM_Q4_K, PM_Q6_K);
+
 namespace {
 
 typedef int      i32x16 __attribute__((ext_vector_type(16)));
@@ -362,7 +365,7 @@ size_t pm_mmq_big_table_bytes(int K, int T) { return (size_t) ((T + 31) / 32) * 
 
 // 0 when pm_launch_mmq_big serves the shape
 int pm_mmq_big_check(int type, int K, int N, int T) {
-    if (type != PM_Q4_K && type != PM_Q6_K) return -1;
+    if (!pm_in_set(MMQ_BIG_TYPES, type)) return -1;
     if (T < 1 || K % 256 || K < 256 || N < 1) return -2;
     if (pm_q8k_row_bytes(K) % 16) return -2;                    // (16-byte DMA pieces of the activation rows: K % 1024 == 0)
     if ((size_t) T * pm_q8k_row_bytes(K) >= ((size_t) 1 << 32) || (size_t) N * pm_weight_row_stride(type, K) >= ((size_t) 1 << 32) ||

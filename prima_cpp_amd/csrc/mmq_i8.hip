@@ -41,6 +41,14 @@
 #include "pm355_kernels.h"
 #include <mutex>
 
+// what pm_launch_mmq_i8 serves: every quantized weight type has an MT<>
+constexpr uint32_t MMQ_I8_TYPES = PM_QUANT_WEIGHTS;
+// ... and the several-matrices-of-one-type launch (pm_launch_mmq_i8_multi): instantiated for Q4_K and Q6_K only; Q5_K, Q8_0 and Q5_0 matrices
+// answer -5 and go one launch each
+constexpr uint32_t MMQ_I8_MULTI_TYPES = pm_type_set(PM_Q4_K, PM_Q6_K);
+// ... and the two-type launch (pm_launch_mmq_i8_dual): Q4_K matrices next to one matrix of one of these (wq | wk + wv of the Q4_K_M files)
+constexpr uint32_t MMQ_I8_DUAL_B_TYPES = pm_type_set(PM_Q6_K, PM_Q5_K);
+
 namespace {
 
 typedef int      i32x16 __attribute__((ext_vector_type(16)));
@@ -710,7 +718,7 @@ size_t pm_mmq_i8_lds_bytes(int type, int K) {
 
 // 0 when pm_launch_mmq_i8 serves this shape
 int pm_mmq_i8_check(int type, int K, int N, int T) {
-    if (type != PM_Q4_K && type != PM_Q5_K && type != PM_Q6_K && type != PM_Q8_0 && type != PM_Q5_0) return -1;
+    if (!pm_in_set(MMQ_I8_TYPES, type)) return -1;
     if (pm_q80_family(type)) return (T < 1 || T > 64 || K % 32 || K < 512 || N < 1) ? -2 : 0;
     if (T < 1 || T > 64 || K % 256 || K < 512 || N < 1) return -2;
     if (pm_mmq_i8_lds_bytes(type, K) > 150 * 1024) return -4;
@@ -941,7 +949,7 @@ bool fill_epi(MmqP & p, const pm_qkv_epi * e, int r0, int r1, int r2) {
 // instantiations have the registers for per-lane row pointers: 238 / 250 VGPRs); -5: not served, launch the jobs one by one. y[j]: [T][N[j]].
 int pm_launch_mmq_i8_multi(int type, int njobs, const void * const * W, const int * N, float * const * Y, const float * const * bias, const void * xq,
                            int K, int T, int reuse_prep, hipStream_t st, const pm_qkv_epi * epi) {
-    if (njobs < 2 || njobs > 3 || T > 64 || (type != PM_Q4_K && type != PM_Q6_K)) return -5;
+    if (njobs < 2 || njobs > 3 || T > 64 || !pm_in_set(MMQ_I8_MULTI_TYPES, type)) return -5;
     // epi: the jobs are wq, wk, wv (three jobs, one pass, even row counts whose heads are whole)
     if (epi && (njobs != 3 || T > 32 || N[0] % epi->dh || N[1] != epi->Hkv * epi->dh || N[2] != N[1])) return -5;
     long total = 0;
@@ -994,7 +1002,7 @@ int pm_launch_mmq_i8_dual(int ta, int na, const void * const * Wa, const int * N
                           int tb, const void * Wb, int Nb, float * Yb, const float * bb, const void * xq, int K, int T, int reuse_prep, hipStream_t st,
                           const pm_qkv_epi * epi) {
     static const bool off = [] { const char * e = getenv("PM355_MMQ_DUAL"); return e && e[0] == '0'; }();
-    if (off || ta != PM_Q4_K || (tb != PM_Q6_K && tb != PM_Q5_K) || na < 1 || na > 3 || T < 1 || T > (tb == PM_Q5_K ? 16 : 32)) return -5;
+    if (off || ta != PM_Q4_K || !pm_in_set(MMQ_I8_DUAL_B_TYPES, tb) || na < 1 || na > 3 || T < 1 || T > (tb == PM_Q5_K ? 16 : 32)) return -5;
     long total = 0;
     for (int j = 0; j < na; ++j) { if (pm_mmq_i8_check(ta, K, Na[j], T)) return -5; total += Na[j]; }
     if (pm_mmq_i8_check(tb, K, Nb, T)) return -5;

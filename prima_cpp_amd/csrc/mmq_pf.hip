@@ -28,6 +28,10 @@
 #include <stdio.h>
 #include <mutex>
 
+// what pm_launch_gemm_pf serves. Q5_0 is left out on purpose: its form of this kernel is still to be built, and pm_launch_gemm_q_h (mmq.hip)
+// takes Q5_0 matrices to the older prompt kernels
+constexpr uint32_t GEMM_PF_TYPES = pm_type_set(PM_Q4_K, PM_Q5_K, PM_Q6_K, PM_Q8_0);
+
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -547,7 +551,7 @@ bool pm_gemm_pf_enabled() {
 
 // 0 when pm_launch_gemm_pf serves (type, K, N, T)
 int pm_gemm_pf_check(int type, int K, int N, int T) {
-    if (type != PM_Q4_K && type != PM_Q5_K && type != PM_Q6_K && type != PM_Q8_0) return -1;
+    if (!pm_in_set(GEMM_PF_TYPES, type)) return -1;
     if ((type == PM_Q8_0 ? K % 128 : K % 256) || K < 512 || N < 1 || N % 4 || T < 1) return -2;
     if (type == PM_Q6_K && PM_Q6K_SCD) return -2;               // (the d's travel as 16-byte pieces = 8 super-blocks of the separate-stream row tail)
     if ((size_t) T * (size_t) K * 2 >= ((size_t) 1 << 32) || (size_t) N * pm_weight_row_stride(type, K) >= ((size_t) 1 << 32)) return -2;   // 32-bit lane offsets

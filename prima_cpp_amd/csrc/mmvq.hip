@@ -29,6 +29,18 @@
 
 using namespace pmv;
 
+// what this file serves: every quantized weight type has a QT<> (mmvq_device.h)
+constexpr uint32_t GEMV_TYPES = PM_QUANT_WEIGHTS;
+// the instantiated (TA, TB) pairs of the fused launch, TA = the type of job 0 (the kernel pre-issues it): one type, or the Q4_K_M mixtures of wq | wk | wv
+// (attn_v is Q6_K / Q5_K next to Q4_K). Q8_0 / Q5_0 jobs need Q8_0-quantized activations, the K-quants Q8_K, and one prologue serves one family:
+// no pair across the two, and Q5_0 next to Q8_0 in one launch is not instantiated. gemv_fill validates against this list, pm_launch_gemv_fused dispatches over it.
+#define PM_GEMV_TYPE_PAIRS(X) X(PM_Q4_K, PM_Q4_K) X(PM_Q5_K, PM_Q5_K) X(PM_Q6_K, PM_Q6_K) X(PM_Q8_0, PM_Q8_0) X(PM_Q5_0, PM_Q5_0) X(PM_Q4_K, PM_Q6_K) X(PM_Q4_K, PM_Q5_K)
+
+// (what the type table says about the mat-vec is what the kernels are compiled with; every type is the TA of some pair)
+#define PM_QT_IS(TA_, TB_) static_assert(QT<TA_>::NV == pm_type_info(TA_).nv && QT<TA_>::ABLK == pm_block_len(TA_), "pm355_types.h and QT<> disagree");
+PM_GEMV_TYPE_PAIRS(PM_QT_IS)
+#undef PM_QT_IS
+
 namespace {
 
 // The first things a workgroup does - the activation loads and the pre-issued weight loads of job 0 - need six values of the argument block. They
@@ -130,9 +142,14 @@ int launch_types(const GemvP & p_in, bool pair, int grid, size_t lds, bool dbg, 
     return 0;
 }
 
-int nv_of(int type) { return type == PM_Q4_K ? QT<PM_Q4_K>::NV : type == PM_Q6_K ? 64 : 32; }
+int nv_of(int type) { return pm_type_info(type).nv; }
 
-bool type_ok(int t) { return t == PM_Q4_K || t == PM_Q5_K || t == PM_Q6_K || t == PM_Q8_0 || t == PM_Q5_0; }
+bool pair_instantiated(int ta, int tb) {
+#define PM_IS(TA_, TB_) if (ta == TA_ && tb == TB_) return true;
+    PM_GEMV_TYPE_PAIRS(PM_IS)
+#undef PM_IS
+    return false;
+}
 
 } // namespace
 
@@ -143,33 +160,18 @@ static int num_cus() {
     return g_num_cus_dev[dv];
 }
 
-int pm_gemv_units_per_row(int type, int64_t K) { return (int) (K / nv_of(type)); }
-
-size_t pm_weight_row_bytes(int type, int64_t K) {
-    switch (type) {
-        case PM_F32:  return (size_t) K * 4;
-        case PM_F16:  return (size_t) K * 2;
-        case PM_Q8_0: return (size_t) (K / 32) * PM_BS_Q8_0;
-        case PM_Q5_0: return (size_t) (K / 32) * PM_BS_Q5_0;
-        case PM_Q4_K: return (size_t) (K / 256) * PM_BS_Q4_K;
-        case PM_Q5_K: return (size_t) (K / 256) * PM_BS_Q5_K;
-        case PM_Q6_K: return (size_t) (K / 256) * PM_BS_Q6_K;
-    }
-    return 0;
-}
+// (a type the mat-vec does not serve answers K / 32 as it always did: the launch that follows refuses it)
+int pm_gemv_units_per_row(int type, int64_t K) { return (int) (K / (nv_of(type) ? nv_of(type) : 32)); }
 
 size_t pm_weight_row_stride(int type, int64_t K) {
-    switch (type) {
-        case PM_Q8_0: { const size_t nb = K / 32;  return nb * 32 + ((nb * 2 + 15) & ~(size_t) 15); }
-        case PM_Q5_0: return pm_q50_row_stride((size_t) (K / 32));
-        case PM_Q6_K: return pm_q6k_row_stride((size_t) (K / 256));
-    }
-    return pm_weight_row_bytes(type, K);
+    if (!pm_type_info(type).pad) return pm_weight_row_bytes(type, K);
+    const size_t nb = (size_t) (K / pm_block_len(type));            // the types with a padded stream, each with its layout's function (pm355_device.h)
+    return type == PM_Q6_K ? pm_q6k_row_stride(nb) : type == PM_Q5_0 ? pm_q50_row_stride(nb) : pm_q80_row_stride(nb);
 }
 
-// Validates a fused job list and fills the kernel argument block. ta <= tb are the (at most two) quant types in the
-// canonical order of the instantiated kernels: (Q4_K,Q4_K) (Q5_K,Q5_K) (Q6_K,Q6_K) (Q8_0,Q8_0) (Q5_0,Q5_0) (Q4_K,Q6_K) (Q4_K,Q5_K); job 0 is
-// always a `ta` job (the kernel pre-issues it). grid_fixed > 0: the caller's grid (attn_wo.hip), else chosen here.
+// Validates a fused job list and fills the kernel argument block. (ta, tb) are the (at most two) quant types in the order of one of the
+// instantiated kernels (PM_GEMV_TYPE_PAIRS); job 0 is always a `ta` job (the kernel pre-issues it). grid_fixed > 0: the caller's grid
+// (attn_wo.hip), else chosen here.
 int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_out, int & tb_out, bool & pair_out, size_t & lds_out, int & grid_out) {
     if (a.njobs < 1 || a.njobs > 3) return -4;
     p = GemvP{};
@@ -182,18 +184,16 @@ int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_
     const bool pair = a.job[0].W2 != nullptr;
     for (int j = 0; j < a.njobs; ++j) {
         const int t = a.job[j].type;
-        if (!type_ok(t)) return -1;
+        if (!pm_in_set(GEMV_TYPES, t)) return -1;
         if (t != ta) { if (tb == ta) tb = t; else if (t != tb) return -1; }
         if ((a.job[j].W2 != nullptr) != pair) return -1;
     }
-    // Q8_0 / Q5_0 jobs need Q8_0-quantized activations, the K-quants need Q8_K: one prologue serves only one family
-    if (pm_q80_family(ta) != pm_q80_family(tb)) return -1;
-    if (pm_q80_family(ta) ? a.K % 32 : a.K % 256) return -2;
+    if (pm_q80_family(ta) != pm_q80_family(tb)) return -1;            // one prologue serves only one activation family
+    if (a.K % pm_block_len(ta)) return -2;
     if (pair && ta != tb) return -1;
-    if (pm_q80_family(ta) && ta != tb) return -1;                    // (Q5_0 next to Q8_0 in one launch: not instantiated)
-    if (ta != tb) {
-        if (ta != PM_Q4_K) { const int t = ta; ta = tb; tb = t; }     // canonical order: Q4_K first
-        if (ta != PM_Q4_K || (tb != PM_Q6_K && tb != PM_Q5_K)) return -1;
+    if (!pair_instantiated(ta, tb)) {                                 // the jobs may come in the other order (wv first)
+        const int t = ta; ta = tb; tb = t;
+        if (!pair_instantiated(ta, tb)) return -1;
     }
     // one workgroup of 16 waves per CU; every workgroup takes an equal slice of the rows of EVERY job
     int grid = grid_fixed > 0 ? grid_fixed : (1024 / PM_GEMV_BLOCK) * num_cus();
@@ -249,7 +249,7 @@ int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_
     }
     if (p.job[0].is_b)                                // the kernel pre-issues job 0 with the TA code path: put a TA job first
         for (int j = 1; j < 3; ++j) if (p.job[j].N > 0 && !p.job[j].is_b) { const GemvJob t = p.job[0]; p.job[0] = p.job[j]; p.job[j] = t; break; }
-    const int ablk = pm_q80_family(ta) ? 32 : 256;
+    const int ablk = pm_block_len(ta);
     size_t lds = (size_t) ((a.K + 15) & ~15) + (size_t) (a.K / 16) * 4 + (size_t) ((a.K / ablk + 3) & ~3) * 4 + (size_t) rows_cap * 4;
     if (att_lds > lds) lds = att_lds;
     if (lds > 150 * 1024) return -4;
@@ -276,16 +276,18 @@ int pm_launch_gemv_fused(const pm_gemv_fused & a, hipStream_t st) {
     const int rc = gemv_fill(a, 0, p, ta, tb, pair, lds, grid);
     if (rc) return rc;
     p.ts = pm_ts_next_slot();
-#define PM_L(TA_, TB_) return launch_types<TA_, TB_>(p, pair, grid, lds, a.dbg_int != nullptr, st, a.epi != nullptr)
-    if (ta == PM_Q4_K && tb == PM_Q4_K) PM_L(PM_Q4_K, PM_Q4_K);
-    if (ta == PM_Q5_K && tb == PM_Q5_K) PM_L(PM_Q5_K, PM_Q5_K);
-    if (ta == PM_Q6_K && tb == PM_Q6_K) PM_L(PM_Q6_K, PM_Q6_K);
-    if (ta == PM_Q8_0 && tb == PM_Q8_0) PM_L(PM_Q8_0, PM_Q8_0);
-    if (ta == PM_Q5_0 && tb == PM_Q5_0) PM_L(PM_Q5_0, PM_Q5_0);
-    if (ta == PM_Q4_K && tb == PM_Q6_K) PM_L(PM_Q4_K, PM_Q6_K);
-    if (ta == PM_Q4_K && tb == PM_Q5_K) PM_L(PM_Q4_K, PM_Q5_K);
+#define PM_L(TA_, TB_) if (ta == TA_ && tb == TB_) return launch_types<TA_, TB_>(p, pair, grid, lds, a.dbg_int != nullptr, st, a.epi != nullptr);
+    PM_GEMV_TYPE_PAIRS(PM_L)
 #undef PM_L
     return -1;
+}
+
+// Column slots of a launch with `left` columns to go: 8 / 4 / 2 share one pass over the weights (gemv_q_cols_kernel), 1 = one launch per column
+int pm_gemv_col_slots(int type, bool pair, int left) {
+    if (left < 2) return 1;
+    if (pair) return pm_in_set(GEMV_PAIR_COLS_TYPES, type) ? 2 : 1;  // pair launches: 2 columns, for Q4_K / Q6_K only (mmvq_device.h)
+    if (left >= 8 && type != PM_Q5_K) return 8;                       // (8 Q5_K columns spill even at 256 VGPRs)
+    return left >= 3 ? 4 : 2;                                         // (3 columns take the 4-slot form with one slot idle: one pass instead of 2 + 1)
 }
 
 // Single-matrix entry with ncols pre-quantized activation columns: groups of 8 / 4 / 2 columns share one pass over the
@@ -301,14 +303,13 @@ int pm_launch_gemv(const pm_gemv_args & a, hipStream_t st) {
         f.job[0].resid = a.resid ? a.resid + (size_t) c * a.y_stride : nullptr;
         const int left = a.ncols - c;
         const bool pair = a.W2 != nullptr;
-        // column slots of the launch: 8 / 4 / 2 (3 columns take the 4-slot form with one slot idle: one pass instead of 2 + 1); pair launches: 2
-        int nc = (a.dbg_int || left < 2) ? 1 : pair ? ((a.type == PM_Q4_K || a.type == PM_Q6_K) ? 2 : 1) : (left >= 8 && a.type != PM_Q5_K ? 8 : left >= 3 ? 4 : 2);   // (8 Q5_K columns spill even at 256 VGPRs)
+        int nc = a.dbg_int ? 1 : pm_gemv_col_slots(a.type, pair, left);
         if (nc > 1) {
             GemvP p; int ta, tb, grid; bool pr; size_t lds1;
             int rc = gemv_fill(f, 0, p, ta, tb, pr, lds1, grid);
             if (rc) return rc;
             // LDS: nc activation columns + nc results per row
-            const int ablk = pm_q80_family(ta) ? 32 : 256;
+            const int ablk = pm_block_len(ta);
             const size_t col = (size_t) ((a.K + 15) & ~15) + (size_t) (a.K / 16) * 4 + (size_t) ((a.K / ablk + 3) & ~3) * 4;
             const size_t rows = (size_t) ((a.N + grid - 1) / grid + 4);
             while (nc > 1 && nc * col + rows * nc * 4 > 150 * 1024) nc /= 2;

@@ -32,7 +32,7 @@ int launch_cols(const GemvP & p, int nc, bool pair, int grid, size_t lds, hipStr
         hipLaunchKernelGGL(kern, dim3(grid), dim3(PM_GEMV_BLOCK), lds, st, p);
     };
     if (pair) {                                       // ffn_gate | ffn_up of a 2-token step: silu(gate) * up per column, one pass over both matrices
-        if constexpr (T == PM_Q4_K || T == PM_Q6_K) { if (nc == 2) { go(gemv_q_cols_kernel<T, 2, true>); return 0; } }
+        if constexpr (pm_in_set(GEMV_PAIR_COLS_TYPES, T)) { if (nc == 2) { go(gemv_q_cols_kernel<T, 2, true>); return 0; } }
         return -1;
     }
     if (nc == 8) {

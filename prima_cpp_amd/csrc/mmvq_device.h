@@ -10,6 +10,9 @@
 
 namespace pmv {
 
+// pair launches (silu(W.x) * (W2.x)) with two activation columns: gemv_q_cols_kernel (mmvq_cols.hip) is instantiated in that form for these types
+// only, and pm_gemv_col_slots (mmvq.hip) asks for it for them only
+constexpr uint32_t GEMV_PAIR_COLS_TYPES = pm_type_set(PM_Q4_K, PM_Q6_K);
 
 struct GemvJob {
     const uint8_t * W; const uint8_t * W2; float * y; const float * bias; const float * resid;

@@ -11,18 +11,10 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include "pm355_types.h"      // pm_type, PM_BS_*, the per-type table
 
 #define PM_QK_K 256
 #define PM_WAVE 64
-
-enum pm_type : int { PM_F32 = 0, PM_F16 = 1, PM_Q5_0 = 6, PM_Q8_0 = 8, PM_Q4_K = 12, PM_Q5_K = 13, PM_Q6_K = 14, PM_Q8_K = 15 };
-
-#define PM_BS_Q5_0 22
-#define PM_BS_Q8_0 34
-#define PM_BS_Q4_K 144
-#define PM_BS_Q5_K 176
-#define PM_BS_Q6_K 210
-#define PM_BS_Q8_K 292
 
 // Q6_K row-SoA tail (round 5): after the three 64-byte-per-block streams (la | lb | qh: nb * 192 bytes) come, per GROUP of 8 blocks, the 8 x 16 int8
 // scales followed by the 8 fp16 super-block scales d (144 bytes): the 2-byte d a mat-vec lane loads sits in the cache lines its scale load has just
@@ -44,8 +36,8 @@ __host__ __device__ inline size_t pm_q6k_row_stride(size_t nb) { return (nb * 21
 __host__ __device__ inline uint32_t pm_q50_qh_off(uint32_t nb) { return nb * 16u; }
 __host__ __device__ inline uint32_t pm_q50_d_off(uint32_t nb) { return nb * 16u + ((nb * 4u + 15u) & ~15u); }
 __host__ __device__ inline size_t pm_q50_row_stride(size_t nb) { return nb * 16 + ((nb * 4 + 15) & ~(size_t) 15) + ((nb * 2 + 15) & ~(size_t) 15); }
-// weights whose vec_dot_type is Q8_0 (32-value activation blocks, ggml.c type_traits): one activation family in every kernel
-__host__ __device__ constexpr bool pm_q80_family(int t) { return t == PM_Q8_0 || t == PM_Q5_0; }
+// Q8_0 row-SoA (repack.hip), nb = K / 32 blocks: qa[nb][16] | qb[nb][16] | d[nb], the d stream padded to 16 bytes
+__host__ __device__ inline size_t pm_q80_row_stride(size_t nb) { return nb * 32 + ((nb * 2 + 15) & ~(size_t) 15); }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));

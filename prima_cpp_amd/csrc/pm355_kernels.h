@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "pm355_types.h"
 
 // index of the current HIP device for the per-device one-time state of the launchers (a process may drive up to 16 GPUs
 // through the plug-in: hipFuncSetAttribute and the CU count are per device, not per process)
@@ -31,15 +32,12 @@ static inline void pm_allow_big_lds(const void * kern, size_t lds) {
 static inline size_t pm_q8k_row_bytes(int K) { return (size_t) K + (size_t) (K / 256) * 4 + (size_t) (K / 16) * 2; }
 static inline size_t pm_q80_row_bytes(int K) { return (size_t) K + (size_t) (K / 32) * 2; }
 
-// bytes of one WEIGHT row in GGUF order (== ggml_row_size)
-size_t pm_weight_row_bytes(int type, int64_t K);
+// (bytes of one WEIGHT row in GGUF order: pm_weight_row_bytes, pm355_types.h)
 // row STRIDE in HBM: == row bytes except that the trailing fp16 scale stream of the row-SoA layouts
 // (Q6_K, Q8_0, Q5_0) is padded to 16 B so every row (and every field stream) starts 16-B aligned for any K
 size_t pm_weight_row_stride(int type, int64_t K);
 int pm_gemv_units_per_row(int type, int64_t K);
   // units of the mat-vec's per-(row, unit) debug partials
-// HBM layout != GGUF block order (repack.hip): Q4_K (12), Q6_K (14), Q8_0 (8), Q5_0 (6)
-static inline bool pm_type_is_repacked(int type) { return type == 12 || type == 14 || type == 8 || type == 6; }
 
 // optional second output of the Q8_K quantizers: the activation tables of the small-batch mat-mul (mmq_i8.hip: per 32-row pass, the F16
 // 16-value sums in MFMA operand order | the transposed block scales) - that mat-mul then needs no prologue launch. base == null: off
@@ -72,6 +70,8 @@ struct pm_gemv_args {
     int32_t * dbg_int;          // debug: per (row, unit) {isum, msum} pairs, or null
 };
 int pm_launch_gemv(const pm_gemv_args & a, hipStream_t st);
+// activation columns one launch of pm_launch_gemv takes in one pass over the weights when `left` columns remain: 8 / 4 / 2, or 1 (one launch per column)
+int pm_gemv_col_slots(int type, bool pair, int left);
 
 // Fused single-token launch: up to 3 matrices (same K) sharing ONE activation row, which is either pre-quantized
 // (xq) or given in f32 (xf) and quantized in the kernel prologue, optionally after rms_norm(xf, eps) * norm_w.

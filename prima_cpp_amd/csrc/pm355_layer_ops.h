@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/prima_mi355.h"
+#include "pm355_types.h"
 
 struct pm_rope_cfg {
     int n_dims, mode /*0 = NORM, 2 = NEOX*/, n_ctx_orig;
@@ -11,12 +12,7 @@ struct pm_rope_cfg {
 };
 void pm_rope_params(pm_rope_cfg & c);
 
-// types the embedding row lookup (layer_ops.hip pm_dequant_elem) decodes; Q5_0 embedding rows are not served (pm355_get_rows and the engine's
-// token embedding refuse them instead of returning zeros)
-static inline bool pm_embed_type_ok(int type) {
-    return type == PM355_TYPE_F32 || type == PM355_TYPE_F16 || type == PM355_TYPE_Q8_0 || type == PM355_TYPE_Q4_K || type == PM355_TYPE_Q5_K ||
-           type == PM355_TYPE_Q6_K;
-}
+// type: one the embedding row lookup decodes (pm_embed_type_ok, pm355_types.h; pm355_get_rows and the engine's token embedding refuse the others)
 void pm_launch_embed(int type, const void * table, int K, const int32_t * tokens, int n_tok, float * out, hipStream_t st);
 void pm_launch_rope_kv_store(const float * q, const float * k, const float * v, float * q_out, float * k_out_f32,
                              void * kc, void * vc, const int32_t * pos0, const int32_t * seq, long seq_stride,

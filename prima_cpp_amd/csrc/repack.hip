@@ -65,7 +65,7 @@ void pm_launch_repack(int type, const void * src, void * dst, int64_t K, int64_t
         if (src != dst) hipMemcpyAsync(dst, src, rb * nrows, hipMemcpyDeviceToDevice, st);
         return;
     }
-    const long nb = pm_q80_family(type) ? K / 32 : K / 256;
+    const long nb = K / pm_block_len(type);
     const long halfs = (long) rb / 2;
     const long n = halfs * nrows;
     hipLaunchKernelGGL(repack_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st,

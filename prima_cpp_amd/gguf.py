@@ -21,9 +21,10 @@ T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F32, T_BOOL, T_STR, T_ARR, T_U64, T_I6
 _SCALAR = {T_U8: "<B", T_I8: "<b", T_U16: "<H", T_I16: "<h", T_U32: "<I", T_I32: "<i", T_F32: "<f", T_BOOL: "<?",
            T_U64: "<Q", T_I64: "<q", T_F64: "<d"}
 
-# ggml types on the path: (block elements, block bytes)   (ggml/src/ggml-common.h)
-F32, F16, Q5_0, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 6, 8, 12, 13, 14
-BLOCK = {F32: (1, 4), F16: (1, 2), Q5_0: (32, 22), Q8_0: (32, 34), Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210)}
+# ggml types on the path: (block elements, block bytes)   (ggml/src/ggml-common.h). The one Python copy of these numbers: lib.py and
+# tests/_bind.py import them from here (the C++ side: csrc/pm355_types.h). Q8_K is the activation format of the K-quants, never a tensor of a file.
+F32, F16, Q5_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 6, 8, 12, 13, 14, 15
+BLOCK = {F32: (1, 4), F16: (1, 2), Q5_0: (32, 22), Q8_0: (32, 34), Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210), Q8_K: (256, 292)}
 
 
 def row_size(t, k):

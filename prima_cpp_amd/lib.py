@@ -8,8 +8,7 @@ import os
 
 import torch  # noqa: F401  (must precede the CDLL below: shared HIP runtime)
 
-F32, F16, Q5_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 6, 8, 12, 13, 14, 15
-_BLOCK = {Q5_0: (32, 22), Q8_0: (32, 34), Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210), Q8_K: (256, 292), F16: (1, 2), F32: (1, 4)}
+from .gguf import F32, F16, Q5_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K, row_size  # noqa: F401  (the type table lives in gguf.py)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -106,12 +105,6 @@ def declare(name, restype, argtypes):
 def check(rc, what=""):
     if rc != 0:
         raise PM355Error(f"{what} failed rc={rc}: {load().pm355_last_error().decode()}")
-
-
-def row_size(t, k):
-    n, b = _BLOCK[t]
-    assert k % n == 0
-    return k // n * b
 
 
 def stream_ptr():

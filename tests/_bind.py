@@ -6,23 +6,20 @@ Nothing in prima_cpp_amd/ imports this module.
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
 
-F32, F16, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 8, 12, 13, 14, 15
+from prima_cpp_amd.gguf import BLOCK, F32, F16, Q5_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K, row_size  # noqa: E402,F401  (the one type table)
+
 TYPE_NAMES = {F32: "f32", F16: "f16", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K", Q8_K: "q8_K"}
-BLOCK = {Q8_0: (32, 34), Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210), Q8_K: (256, 292),
-         F16: (1, 2), F32: (1, 4)}
+# (without Q5_0: this list parametrises tests whose oracle calls do not all serve it; tests/test_gpu_q5_0.py covers Q5_0)
 QUANT_TYPES = [Q4_K, Q5_K, Q6_K, Q8_0]
-
-
-def row_size(t, k):
-    n, b = BLOCK[t]
-    assert k % n == 0
-    return k // n * b
 
 
 def vec_dot_type(t):
