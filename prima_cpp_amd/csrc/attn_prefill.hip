@@ -184,7 +184,9 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(PfP p) {
     }
     {
         const float mo = __shfl_xor(m, 32), lo = __shfl_xor(l, 32);
-        const float mn = fmaxf(m, mo);           // key 0 is always visible: mn is finite
+        // every query sees at least one cell, so mn is finite - but in mask mode one HALF may arrive with m = -inf, l = 0 (parallel sequences, holes:
+        // all visible keys have k % 8 < 4, or >= 4; tests/test_gpu_attn_masked.py): its term is dropped, not multiplied by expf(-inf)
+        const float mn = fmaxf(m, mo);
         l = (m == -INFINITY ? 0.0f : l * expf(m - mn)) + (mo == -INFINITY ? 0.0f : lo * expf(mo - mn));
         m = mn;
     }

@@ -190,6 +190,24 @@ def attn_prefill(q, k_cache, v_cache, pos0, n_head, n_head_kv, head_dim, n_ctx, 
     return out
 
 
+def attn_prefill_masked(q, k_cache, v_cache, mask, n_tokens, n_head, n_head_kv, head_dim, n_ctx, n_kv, scale, mask_stride=None, flags=0,
+                        out=None):
+    """Multi-token attention on MFMA with the additive KQ_mask (pm355_attn_prefill_masked_ex): query t attends cells [0, n_kv) with mask row t,
+    rows mask_stride elements apart (default: mask.shape[-1]). flags: ATTN_V_ROWMAJOR (V cache [n_ctx][n_head_kv*head_dim]) | ATTN_MASK_F16.
+    out: optional f32 [n_tokens, n_head*head_dim] to write into (tests of the refusals pre-fill it). mask=None is passed on as NULL."""
+    import ctypes as C
+    lib = L.load()
+    lib.pm355_attn_prefill_masked_ex.restype = C.c_int
+    lib.pm355_attn_prefill_masked_ex.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p]
+    if mask_stride is None:
+        mask_stride = mask.shape[-1]
+    if out is None:
+        out = torch.empty((n_tokens, n_head * head_dim), dtype=torch.float32, device=q.device)
+    check(lib.pm355_attn_prefill_masked_ex(ptr(q), ptr(k_cache), ptr(v_cache), ptr(mask), int(mask_stride), ptr(out), n_tokens, n_head, n_head_kv,
+                                           head_dim, n_ctx, n_kv, float(scale), int(flags), stream_ptr()), "attn_prefill_masked")
+    return out
+
+
 def argmax(x):
     lib = L.load()
     idx = torch.empty(1, dtype=torch.int32, device=x.device)
