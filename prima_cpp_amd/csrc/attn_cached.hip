@@ -148,29 +148,24 @@ __global__ __launch_bounds__(256) void attn_cached_kernel(AttnP a_in) {
 } // namespace
 
 void pm_launch_rope_table(const pm_rope_cfg & c, const int32_t * pos, const int32_t * seq, const float * freq_factors, float * tab, hipStream_t st, int n_tok) {
-    RopeP r;
-    r.n_dims = c.n_dims; r.mode = c.mode; r.n_ctx_orig = c.n_ctx_orig; r.theta_scale = c.theta_scale;
-    r.freq_scale = c.freq_scale; r.ext_factor = c.ext_factor; r.attn_factor = c.attn_factor; r.corr0 = c.corr0; r.corr1 = c.corr1;
-    hipLaunchKernelGGL(rope_table_kernel, dim3(n_tok < 1 ? 1 : n_tok), dim3(128), 0, st, r, pos, seq, freq_factors, tab);
+    hipLaunchKernelGGL(rope_table_kernel, dim3(n_tok < 1 ? 1 : n_tok), dim3(128), 0, st, rope_p(c), pos, seq, freq_factors, tab);
 }
 
-// q = rotated, F16-rounded query rows; caches already hold this token. Same arguments as pm_launch_attn_rope_fused otherwise.
-int pm_launch_attn_cached(const float * q, void * kc, void * vc, const int32_t * pos0, const int32_t * seq, long seq_stride, float * out,
-                          int H, int Hkv, int dh, int n_ctx, float scale, hipStream_t st, const int32_t * dyn, const void * mask,
-                          int max_keys, int v_rowmajor, int mask_f16, int n_tok) {
-    if ((dh != 64 && dh != 128 && dh != 256) || n_ctx % 8 || n_tok < 1 || (n_tok > 1 && dyn)) return -1;
-    const size_t lds = (size_t) (4 * dh + (v_rowmajor ? 2048 : 256) + (max_keys > 0 ? ((max_keys + 7) & ~7) : n_ctx) + 8) * 4;
-    if (lds > 150 * 1024) return -1;
-    RopeP r = {};
-    if (!pos0) pos0 = dyn;                       // ggml-graph mode: cells come from dyn; keep every pointer the kernel may touch valid
+// q = rotated, F16-rounded query rows; caches already hold this token
+int pm_launch_attn_cached(const pm_attn_tok & t, hipStream_t st) {
+    const int dh = t.dh;
+    if ((dh != 64 && dh != 128 && dh != 256) || t.n_ctx % 8 || t.n_tok < 1 || (t.n_tok > 1 && t.dyn)) return -1;
+    const size_t lds = pm_attn_head_lds(dh, t.n_ctx, t.v_rowmajor, t.cells);
+    if (lds > PM_ATTN_LDS_MAX || t.rope || t.k_q8 || t.v_q8) return -1;
+    const int32_t * pos0 = t.pos ? t.pos : t.dyn;   // ggml-graph mode: cells come from dyn; keep every pointer the kernel may touch valid
     if (!pos0) return -1;
     auto launch = [&](auto kern) {
         if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        AttnP a = {q, nullptr, nullptr, (uint16_t *) kc, (uint16_t *) vc, pos0, seq, seq_stride, nullptr, out, H, Hkv, n_ctx, scale, r, dyn,
-                   (const float *) mask, mask_f16, pm_ts_next_slot()};
-        hipLaunchKernelGGL(kern, dim3(H, n_tok), dim3(256), lds, st, a);
+        AttnP a = {t.q, nullptr, nullptr, (uint16_t *) t.kc, (uint16_t *) t.vc, pos0, t.seq, t.seq_stride, nullptr, t.out, t.H, t.Hkv, t.n_ctx, t.scale,
+                   RopeP{}, t.dyn, (const float *) t.mask, t.mask_f16, pm_ts_next_slot()};
+        hipLaunchKernelGGL(kern, dim3(t.H, t.n_tok), dim3(256), lds, st, a);
     };
-    if (v_rowmajor) {
+    if (t.v_rowmajor) {
         if (dh == 64) launch(attn_cached_kernel<64, 1>);
         else if (dh == 128) launch(attn_cached_kernel<128, 1>);
         else launch(attn_cached_kernel<256, 1>);

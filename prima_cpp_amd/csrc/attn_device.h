@@ -2,11 +2,18 @@
 // layer_ops.hip. Design notes: layer_ops.hip.
 #pragma once
 #include "pm355_device.h"
+#include "pm355_layer_ops.h"
 
 struct RopeP {
     int n_dims, mode, n_ctx_orig;
     float theta_scale, freq_scale, ext_factor, attn_factor, corr0, corr1;
 };
+inline RopeP rope_p(const pm_rope_cfg & c) {
+    RopeP r;
+    r.n_dims = c.n_dims; r.mode = c.mode; r.n_ctx_orig = c.n_ctx_orig; r.theta_scale = c.theta_scale;
+    r.freq_scale = c.freq_scale; r.ext_factor = c.ext_factor; r.attn_factor = c.attn_factor; r.corr0 = c.corr0; r.corr1 = c.corr1;
+    return r;
+}
 
 __device__ __forceinline__ void rope_cs(const RopeP & r, float pos, int pair, const float * ff, float & c, float & s) {
     float theta = pos;

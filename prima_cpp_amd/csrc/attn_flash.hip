@@ -340,24 +340,21 @@ size_t pm_attn_flash_qrot_offset(int H, int Hkv, int dh, int n_ctx) {
 
 // q, k, v = the RAW projections of the token; RoPE, KV store and attention over cells [0, n_kv) happen in this one launch.
 // max_cells bounds the cells attended (sizes the grid: spans beyond n_kv exit at once); 0 = n_ctx. -1: unsupported shape.
-int pm_launch_attn_flash(const float * q, const float * k, const float * v, void * kc, void * vc, const int32_t * pos0, const int32_t * seq,
-                         long seq_stride, const float * freq_factors, float * out, float * scratch, int H, int Hkv, int dh, int n_ctx,
-                         float scale, const pm_rope_cfg & c, hipStream_t st, const int32_t * dyn, const void * mask, int v_rowmajor, int mask_f16,
-                         int max_cells) {
+int pm_launch_attn_flash(const pm_attn_tok & a, hipStream_t st) {
+    const int H = a.H, Hkv = a.Hkv, dh = a.dh, n_ctx = a.n_ctx; float * const scratch = a.scratch;
     if ((dh != 64 && dh != 128) || H % Hkv || H / Hkv > RMAX || n_ctx % 8 || !scratch) return -1;
+    if (!a.rope || a.k_q8 || a.v_q8 || a.n_tok != 1) return -1;
     const int nspan_max = (n_ctx + CK - 1) / CK;
-    const int cells = max_cells > 0 && max_cells < n_ctx ? max_cells : n_ctx;
+    const int cells = a.cells > 0 && a.cells < n_ctx ? a.cells : n_ctx;
     // span = keys per workgroup: 128 up to 8k cells, then grown so that a KV head never has more than 64 partials to merge
     int span = CK;
     while ((cells + span - 1) / span > 64) span *= 2;
     FlashP p = {};
-    p.q = q; p.k = k; p.v = v; p.kc = (uint16_t *) kc; p.vc = (uint16_t *) vc; p.pos0_ptr = pos0; p.seq_ptr = seq; p.seq_stride = seq_stride;
-    p.ff = freq_factors; p.out = out;
+    p.q = a.q; p.k = a.k; p.v = a.v; p.kc = (uint16_t *) a.kc; p.vc = (uint16_t *) a.vc; p.pos0_ptr = a.pos; p.seq_ptr = a.seq; p.seq_stride = a.seq_stride;
+    p.ff = a.freq_factors; p.out = a.out;
     p.M = scratch; p.L = p.M + (size_t) H * nspan_max; p.P = p.L + (size_t) H * nspan_max; p.ticket = (unsigned *) (p.P + (size_t) nspan_max * H * dh);
-    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nspan = nspan_max; p.span = span; p.scale = scale;
-    p.r.n_dims = c.n_dims; p.r.mode = c.mode; p.r.n_ctx_orig = c.n_ctx_orig; p.r.theta_scale = c.theta_scale; p.r.freq_scale = c.freq_scale;
-    p.r.ext_factor = c.ext_factor; p.r.attn_factor = c.attn_factor; p.r.corr0 = c.corr0; p.r.corr1 = c.corr1;
-    p.dyn = dyn; p.mask = mask; p.mask_f16 = mask_f16; p.vm = v_rowmajor ? 1 : 0;
+    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nspan = nspan_max; p.span = span; p.scale = a.scale; p.r = rope_p(*a.rope);
+    p.dyn = a.dyn; p.mask = a.mask; p.mask_f16 = a.mask_f16; p.vm = a.v_rowmajor ? 1 : 0;
     const dim3 grid((cells + span - 1) / span, Hkv);
     if (dh == 128) {
         if (p.vm) hipLaunchKernelGGL((attn_flash_kernel<128, 1>), grid, dim3(256), 0, st, p);

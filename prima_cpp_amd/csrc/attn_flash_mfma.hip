@@ -398,16 +398,16 @@ int pm_attn_flash_cached_ok(int H, int Hkv, int dh, int n_ctx) {
     return Hkv * parts <= 2 * pm_device_cus() ? 0 : -1;
 }
 
-int pm_launch_attn_flash_cached(const float * q, void * kc, void * vc, const int32_t * pos0, const int32_t * seq, long seq_stride, float * out,
-                                float * scratch, int H, int Hkv, int dh, int n_ctx, float scale, hipStream_t st, const int32_t * dyn,
-                                const void * mask, int mask_f16, int max_cells, int v_rowmajor, int k_q8, int v_q8) {
-    if (!scratch || pm_attn_flash_cached_ok(H, Hkv, dh, n_ctx)) return -1;
-    if ((k_q8 || v_q8) && (!v_rowmajor || seq)) return -1;          // Q8_0 caches: flash-attention layout (row-major V), one sequence slab
-    if (!pos0) pos0 = dyn;
+int pm_launch_attn_flash_cached(const pm_attn_tok & a, hipStream_t st) {
+    const int H = a.H, Hkv = a.Hkv, dh = a.dh, n_ctx = a.n_ctx;
+    const bool k_q8 = a.k_q8, v_q8 = a.v_q8, v_rowmajor = a.v_rowmajor; float * const scratch = a.scratch;
+    if (!scratch || pm_attn_flash_cached_ok(H, Hkv, dh, n_ctx) || a.rope || a.n_tok != 1) return -1;
+    if ((k_q8 || v_q8) && (!v_rowmajor || a.seq)) return -1;        // Q8_0 caches: flash-attention layout (row-major V), one sequence slab
+    const int32_t * pos0 = a.pos ? a.pos : a.dyn;
     if (!pos0) return -1;
     const int CK = 128;
     const int nspan_max = (n_ctx + CK - 1) / CK;
-    const int cells = max_cells > 0 && max_cells < n_ctx ? max_cells : n_ctx;
+    const int cells = a.cells > 0 && a.cells < n_ctx ? a.cells : n_ctx;
     // spans: 128 keys each until the KV heads together fill the CUs (256 workgroups: 32 spans per head at 8 KV heads - measured against 64
     // and 16 at 8k .. 32k cells), then longer spans; never more than 64 partials per head (the mergers' LDS tables)
     int span = CK, parts = 256 / Hkv;
@@ -417,10 +417,10 @@ int pm_launch_attn_flash_cached(const float * q, void * kc, void * vc, const int
     if (parts_env) parts = parts_env;
     while ((cells + span - 1) / span > parts) span *= 2;
     FlashM p = {};
-    p.q = q; p.kc = (const uint16_t *) kc; p.vc = (const uint16_t *) vc; p.pos0_ptr = pos0; p.seq_ptr = seq; p.seq_stride = seq_stride; p.out = out;
+    p.q = a.q; p.kc = (const uint16_t *) a.kc; p.vc = (const uint16_t *) a.vc; p.pos0_ptr = pos0; p.seq_ptr = a.seq; p.seq_stride = a.seq_stride; p.out = a.out;
     p.M = scratch; p.L = p.M + (size_t) H * nspan_max; p.P = p.L + (size_t) H * nspan_max; p.ticket = (unsigned *) (p.P + (size_t) nspan_max * H * dh) + Hkv + 16;    // (behind attn_flash.hip's tickets, which must read 0 between its launches)
-    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nspan = nspan_max; p.span = span; p.scale = scale;
-    p.dyn = dyn; p.mask = mask; p.mask_f16 = mask_f16; p.ts = pm_ts_next_slot();
+    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nspan = nspan_max; p.span = span; p.scale = a.scale;
+    p.dyn = a.dyn; p.mask = a.mask; p.mask_f16 = a.mask_f16; p.ts = pm_ts_next_slot();
     const dim3 grid(Hkv, (cells + span - 1) / span);
     if (k_q8 || v_q8) {
 #define PM_FQ8(DH_) do { \

@@ -430,16 +430,15 @@ int pm_launch_flash_attn_ext_q8(const pm355_tensor * q, const pm355_tensor * k, 
     return 0;
 }
 
-// one token, long context: RoPE + (quantizing) KV store in one small launch (q_rot receives the operand rows of the K.q product), then the caller
+// one token, long context: RoPE + (quantizing) KV store in one small launch (t.out receives the operand rows of the K.q product), then the caller
 // runs pm_launch_attn_flash_cached over the cached cells. Row-major caches. -1: unsupported
-int pm_launch_q8_token_prep(const float * q, const float * k, const float * v, void * kc, void * vc, const int32_t * pos, const int32_t * dyn, const float * ff,
-                            float * q_rot, int H, int Hkv, int dh, int n_ctx, const pm_rope_cfg & c, int k_q8, int v_q8, hipStream_t st) {
-    if ((dh != 64 && dh != 128) || H % Hkv || (!k_q8 && !v_q8) || !dyn || !q_rot) return -1;
+int pm_launch_q8_token_prep(const pm_attn_tok & t, hipStream_t st) {
+    const int H = t.H, dh = t.dh; const bool k_q8 = t.k_q8, v_q8 = t.v_q8;
+    if ((dh != 64 && dh != 128) || H % t.Hkv || (!k_q8 && !v_q8) || !t.dyn || !t.out || !t.rope || !t.v_rowmajor || t.seq || t.n_tok != 1) return -1;
     Q8TokP a = {};
-    a.q = q; a.k = k; a.v = v; a.kc = (uint8_t *) kc; a.vc = (uint8_t *) vc; a.pos = pos; a.dyn = dyn; a.ff = ff; a.H = H; a.Hkv = Hkv; a.n_ctx = n_ctx;
-    a.r.n_dims = c.n_dims; a.r.mode = c.mode; a.r.n_ctx_orig = c.n_ctx_orig; a.r.theta_scale = c.theta_scale; a.r.freq_scale = c.freq_scale;
-    a.r.ext_factor = c.ext_factor; a.r.attn_factor = c.attn_factor; a.r.corr0 = c.corr0; a.r.corr1 = c.corr1;
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(H), dim3(dh), 0, st, a, q_rot); };
+    a.q = t.q; a.k = t.k; a.v = t.v; a.kc = (uint8_t *) t.kc; a.vc = (uint8_t *) t.vc; a.pos = t.pos; a.dyn = t.dyn; a.ff = t.freq_factors;
+    a.H = H; a.Hkv = t.Hkv; a.n_ctx = t.n_ctx; a.r = rope_p(*t.rope);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(H), dim3(dh), 0, st, a, t.out); };
     if (dh == 128) {
         if (k_q8 && v_q8) go(q8_token_prep_kernel<128, true, true>); else if (k_q8) go(q8_token_prep_kernel<128, true, false>); else go(q8_token_prep_kernel<128, false, true>);
     } else {
@@ -449,18 +448,16 @@ int pm_launch_q8_token_prep(const float * q, const float * k, const float * v, v
 }
 
 // one token, one launch: RoPE + KV store (quantizing) + attention over cells [0, dyn[1]); row-major caches. -1: unsupported
-int pm_launch_attn_q8_token(const float * q, const float * k, const float * v, void * kc, void * vc, const int32_t * pos, const int32_t * dyn,
-                            const void * mask, int mask_f16, const float * ff, float * out, int H, int Hkv, int dh, int n_ctx, float scale,
-                            const pm_rope_cfg & c, int k_q8, int v_q8, int max_keys, hipStream_t st) {
-    if ((dh != 64 && dh != 128) || H % Hkv || (!k_q8 && !v_q8) || !dyn) return -1;
-    const int keys = max_keys > 0 ? max_keys : n_ctx;
+int pm_launch_attn_q8_token(const pm_attn_tok & t, hipStream_t st) {
+    const int H = t.H, dh = t.dh; const bool k_q8 = t.k_q8, v_q8 = t.v_q8;
+    if ((dh != 64 && dh != 128) || H % t.Hkv || (!k_q8 && !v_q8) || !t.dyn || !t.rope || !t.v_rowmajor || t.seq || t.n_tok != 1) return -1;
+    // (this kernel's own LDS layout - three head rows, always the row-major V slots - not pm_attn_head_lds)
+    const int keys = t.cells > 0 ? t.cells : t.n_ctx;
     const size_t lds = ((size_t) 3 * dh + 2048 + (size_t) ((keys + 7) & ~7) + 8) * 4;
-    if (lds > 150 * 1024) return -1;
+    if (lds > PM_ATTN_LDS_MAX) return -1;
     Q8TokP a;
-    a.q = q; a.k = k; a.v = v; a.kc = (uint8_t *) kc; a.vc = (uint8_t *) vc; a.pos = pos; a.dyn = dyn; a.mask = mask; a.mask_f16 = mask_f16;
-    a.ff = ff; a.out = out; a.H = H; a.Hkv = Hkv; a.n_ctx = n_ctx; a.scale = scale;
-    a.r.n_dims = c.n_dims; a.r.mode = c.mode; a.r.n_ctx_orig = c.n_ctx_orig; a.r.theta_scale = c.theta_scale; a.r.freq_scale = c.freq_scale;
-    a.r.ext_factor = c.ext_factor; a.r.attn_factor = c.attn_factor; a.r.corr0 = c.corr0; a.r.corr1 = c.corr1;
+    a.q = t.q; a.k = t.k; a.v = t.v; a.kc = (uint8_t *) t.kc; a.vc = (uint8_t *) t.vc; a.pos = t.pos; a.dyn = t.dyn; a.mask = t.mask; a.mask_f16 = t.mask_f16;
+    a.ff = t.freq_factors; a.out = t.out; a.H = H; a.Hkv = t.Hkv; a.n_ctx = t.n_ctx; a.scale = t.scale; a.r = rope_p(*t.rope);
     auto go = [&](auto kern) { set_lds((const void *) kern, lds); hipLaunchKernelGGL(kern, dim3(H), dim3(256), lds, st, a); };
     if (dh == 128) {
         if (k_q8 && v_q8) go(attn_q8_token_kernel<128, true, true>); else if (k_q8) go(attn_q8_token_kernel<128, true, false>); else go(attn_q8_token_kernel<128, false, true>);

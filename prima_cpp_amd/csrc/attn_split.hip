@@ -300,20 +300,17 @@ size_t pm_attn_split_scratch_floats(int H, int dh, int n_ctx) {
 
 // rope == nullptr: q = this token's ROTATED queries [H*dh] f32 and the caches already hold its K row / V column (k, v unused).
 // rope != nullptr: q, k, v = the RAW projections; the rotation, the KV store and the attention are done here (3 launches).
-int pm_launch_attn_split(const float * q, const float * k, const float * v, void * kc, void * vc, const int32_t * pos0, const int32_t * seq,
-                         long seq_stride, const float * freq_factors, float * out, float * scratch, int H, int Hkv, int dh, int n_ctx,
-                         float scale, const pm_rope_cfg * rope, hipStream_t st, const int32_t * dyn, const void * mask, int v_rowmajor, int mask_f16) {
-    if ((dh != 64 && dh != 128) || H % Hkv || H / Hkv > RMAX || n_ctx % 8 || !scratch) return -1;
+int pm_launch_attn_split(const pm_attn_tok & a, hipStream_t st) {
+    const int H = a.H, Hkv = a.Hkv, dh = a.dh, n_ctx = a.n_ctx;
+    if ((dh != 64 && dh != 128) || H % Hkv || H / Hkv > RMAX || n_ctx % 8 || !a.scratch || a.k_q8 || a.v_q8 || a.cells || a.n_tok != 1) return -1;
     const int nchunk = (n_ctx + CK - 1) / CK;
     SplitP p = {};
-    p.q = q; p.kc = (const uint16_t *) kc; p.vc = (const uint16_t *) vc; p.pos0_ptr = pos0; p.seq_ptr = seq; p.seq_stride = seq_stride;
-    p.out = out; p.S = scratch; p.M = p.S + (size_t) H * n_ctx; p.L = p.M + (size_t) H * nchunk; p.P = p.L + (size_t) H * nchunk;
-    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nchunk = nchunk; p.scale = scale; p.dyn = dyn; p.mask = mask; p.mask_f16 = mask_f16; p.vm = v_rowmajor ? 1 : 0;
-    if (rope) {
-        const pm_rope_cfg & c = *rope;
-        p.r.n_dims = c.n_dims; p.r.mode = c.mode; p.r.n_ctx_orig = c.n_ctx_orig; p.r.theta_scale = c.theta_scale;
-        p.r.freq_scale = c.freq_scale; p.r.ext_factor = c.ext_factor; p.r.attn_factor = c.attn_factor; p.r.corr0 = c.corr0; p.r.corr1 = c.corr1;
-        p.k = k; p.v = v; p.ff = freq_factors; p.kc_w = (uint16_t *) kc; p.vc_w = (uint16_t *) vc; p.do_rope = 1;
+    p.q = a.q; p.kc = (const uint16_t *) a.kc; p.vc = (const uint16_t *) a.vc; p.pos0_ptr = a.pos; p.seq_ptr = a.seq; p.seq_stride = a.seq_stride;
+    p.out = a.out; p.S = a.scratch; p.M = p.S + (size_t) H * n_ctx; p.L = p.M + (size_t) H * nchunk; p.P = p.L + (size_t) H * nchunk;
+    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nchunk = nchunk; p.scale = a.scale; p.dyn = a.dyn; p.mask = a.mask; p.mask_f16 = a.mask_f16; p.vm = a.v_rowmajor ? 1 : 0;
+    if (a.rope) {
+        p.r = rope_p(*a.rope);
+        p.k = a.k; p.v = a.v; p.ff = a.freq_factors; p.kc_w = (uint16_t *) a.kc; p.vc_w = (uint16_t *) a.vc; p.do_rope = 1;
     }
     const dim3 grid(nchunk, Hkv);
     if (dh == 128) {

@@ -348,17 +348,15 @@ int pm355_rope_kv_store(const float * q, const float * k, const float * v, float
                         void * kc, void * vc, const int32_t * d_pos0, const float * ff, int n_tokens, int H, int Hkv, int dh,
                         int n_ctx, const pm355_rope_params * rp, pm355_stream_t st) {
     if (!rp || rp->n_dims % 2 || rp->n_dims > dh || dh % 2) return fail(PM355_E_SHAPE, "rope: n_dims");
-    pm_rope_cfg c;
-    c.n_dims = rp->n_dims; c.mode = rp->mode; c.n_ctx_orig = rp->n_ctx_orig; c.freq_base = rp->freq_base; c.freq_scale = rp->freq_scale;
-    c.ext_factor = rp->ext_factor; c.attn_factor = rp->attn_factor; c.beta_fast = rp->beta_fast; c.beta_slow = rp->beta_slow;
-    pm_rope_params(c);
-    pm_launch_rope_kv_store(q, k, v, q_out, k_out_f32, kc, vc, d_pos0, nullptr, 0, ff, n_tokens, H, Hkv, dh, n_ctx, c, S(st));
+    pm_launch_rope_kv_store(q, k, v, q_out, k_out_f32, kc, vc, d_pos0, nullptr, 0, ff, n_tokens, H, Hkv, dh, n_ctx, pm_rope_cfg_of(*rp), S(st));
     HIP_TRY(hipGetLastError());
     return 0;
 }
 int pm355_attn_decode(const float * q, const void * kc, const void * vc, const int32_t * d_pos0, float * out, int n_tokens,
                       int H, int Hkv, int dh, int n_ctx, float kq_scale, pm355_stream_t st) {
-    if (pm_launch_attn_decode(q, kc, vc, d_pos0, nullptr, 0, out, n_tokens, H, Hkv, dh, n_ctx, kq_scale, S(st)))
+    pm_attn_tok t = {};
+    t.q = q; t.kc = (void *) kc; t.vc = (void *) vc; t.pos = d_pos0; t.out = out; t.n_tok = n_tokens; t.H = H; t.Hkv = Hkv; t.dh = dh; t.n_ctx = n_ctx; t.scale = kq_scale;
+    if (pm_launch_attn_decode(t, S(st)))
         return fail(PM355_E_RANGE, "attn_decode: n_ctx/head_dim unsupported (LDS budget 150 KB, multiples of 8)");
     HIP_TRY(hipGetLastError());
     return 0;
@@ -369,7 +367,10 @@ size_t pm355_attn_split_scratch_floats(int H, int dh, int n_ctx) {       // (cov
 }
 int pm355_attn_decode_split(const float * q_rot, const void * kc, const void * vc, const int32_t * d_pos0, float * out, float * scratch,
                             int H, int Hkv, int dh, int n_ctx, float kq_scale, pm355_stream_t st) {
-    if (pm_launch_attn_split(q_rot, nullptr, nullptr, (void *) kc, (void *) vc, d_pos0, nullptr, 0, nullptr, out, scratch, H, Hkv, dh, n_ctx, kq_scale, nullptr, S(st)))
+    pm_attn_tok t = {};
+    t.q = q_rot; t.kc = (void *) kc; t.vc = (void *) vc; t.pos = d_pos0; t.out = out; t.scratch = scratch;
+    t.H = H; t.Hkv = Hkv; t.dh = dh; t.n_ctx = n_ctx; t.scale = kq_scale;
+    if (pm_launch_attn_split(t, S(st)))
         return fail(PM355_E_RANGE, "attn_decode_split: head_dim 64/128, at most 8 query heads per KV head, n_ctx % 8 == 0, scratch required");
     HIP_TRY(hipGetLastError());
     return 0;
@@ -398,25 +399,18 @@ int pm355_attn_rope_fused(const float * q, const float * k, const float * v, voi
                           const float * ff, float * out, int H, int Hkv, int dh, int n_ctx, float kq_scale,
                           const pm355_rope_params * rp, pm355_stream_t st) {
     if (!rp || rp->n_dims % 2 || rp->n_dims > dh) return fail(PM355_E_SHAPE, "attn_rope_fused: n_dims");
-    pm_rope_cfg c;
-    c.n_dims = rp->n_dims; c.mode = rp->mode; c.n_ctx_orig = rp->n_ctx_orig; c.freq_base = rp->freq_base; c.freq_scale = rp->freq_scale;
-    c.ext_factor = rp->ext_factor; c.attn_factor = rp->attn_factor; c.beta_fast = rp->beta_fast; c.beta_slow = rp->beta_slow;
-    pm_rope_params(c);
-    if (pm_launch_attn_rope_fused(q, k, v, kc, vc, d_pos0, nullptr, 0, ff, out, H, Hkv, dh, n_ctx, kq_scale, c, S(st)))
+    const pm_rope_cfg c = pm_rope_cfg_of(*rp);
+    pm_attn_tok t = {};
+    t.q = q; t.k = k; t.v = v; t.kc = kc; t.vc = vc; t.pos = d_pos0; t.freq_factors = ff; t.out = out;
+    t.H = H; t.Hkv = Hkv; t.dh = dh; t.n_ctx = n_ctx; t.scale = kq_scale; t.rope = &c;
+    if (pm_launch_attn_rope_fused(t, S(st)))
         return fail(PM355_E_UNSUPPORTED, "attn_rope_fused: head_dim must be 64/128/256, n_ctx % 8 == 0 and fit LDS");
     HIP_TRY(hipGetLastError());
     return 0;
 }
-static pm_rope_cfg rope_cfg_of(const pm355_rope_params * rp) {
-    pm_rope_cfg c;
-    c.n_dims = rp->n_dims; c.mode = rp->mode; c.n_ctx_orig = rp->n_ctx_orig; c.freq_base = rp->freq_base; c.freq_scale = rp->freq_scale;
-    c.ext_factor = rp->ext_factor; c.attn_factor = rp->attn_factor; c.beta_fast = rp->beta_fast; c.beta_slow = rp->beta_slow;
-    pm_rope_params(c);
-    return c;
-}
 int pm355_rope_table(const pm355_rope_params * rp, const int32_t * d_pos, const float * ff, float * table, pm355_stream_t st) {
     if (!rp || rp->n_dims % 2 || rp->n_dims > 256 || !d_pos || !table) return fail(PM355_E_SHAPE, "rope_table: n_dims (even, <= 256), d_pos and table required");
-    pm_launch_rope_table(rope_cfg_of(rp), d_pos, nullptr, ff, table, S(st));
+    pm_launch_rope_table(pm_rope_cfg_of(*rp), d_pos, nullptr, ff, table, S(st));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -514,8 +508,11 @@ int pm355_mul_mat_vec_qkv_check(const pm355_matvec_job * jobs, int64_t K, int n_
 int pm355_attn_cached(const float * q_rot, void * kc, void * vc, const int32_t * d_pos, const int32_t * d_cell_nkv, const void * mask,
                       float * out, int H, int Hkv, int dh, int n_ctx, float kq_scale, int max_keys, int flags, pm355_stream_t st) {
     if (!q_rot || !kc || !vc || !out || (!d_pos && !d_cell_nkv)) return fail(PM355_E_SHAPE, "attn_cached: null pointer");
-    if (pm_launch_attn_cached(q_rot, kc, vc, d_pos, nullptr, 0, out, H, Hkv, dh, n_ctx, kq_scale, S(st), d_cell_nkv, mask, max_keys,
-                              flags & PM355_ATTN_V_ROWMAJOR, flags & PM355_ATTN_MASK_F16))
+    pm_attn_tok t = {};
+    t.q = q_rot; t.kc = kc; t.vc = vc; t.pos = d_pos; t.dyn = d_cell_nkv; t.mask = mask; t.out = out;
+    t.H = H; t.Hkv = Hkv; t.dh = dh; t.n_ctx = n_ctx; t.scale = kq_scale; t.cells = max_keys;
+    t.v_rowmajor = flags & PM355_ATTN_V_ROWMAJOR; t.mask_f16 = flags & PM355_ATTN_MASK_F16;
+    if (pm_launch_attn_cached(t, S(st)))
         return fail(PM355_E_UNSUPPORTED, "attn_cached: head_dim must be 64/128/256, n_ctx % 8 == 0 and max_keys fit LDS");
     HIP_TRY(hipGetLastError());
     return 0;
@@ -524,9 +521,12 @@ int pm355_attn_cached_long(const float * q_rot, void * kc, void * vc, const int3
                            float * out, float * scratch, int H, int Hkv, int dh, int n_ctx, float kq_scale, int max_cells, int flags, pm355_stream_t st) {
     if (!q_rot || !kc || !vc || !out || !scratch || (!d_pos && !d_cell_nkv)) return fail(PM355_E_SHAPE, "attn_cached_long: null pointer");
     if (flags & ~(PM355_ATTN_MASK_F16 | PM355_ATTN_V_ROWMAJOR | PM355_ATTN_K_Q8_0 | PM355_ATTN_V_Q8_0)) return fail(PM355_E_UNSUPPORTED, "attn_cached_long: unknown flag");
-    if (pm_launch_attn_flash_cached(q_rot, kc, vc, d_pos, nullptr, 0, out, scratch, H, Hkv, dh, n_ctx, kq_scale, S(st), d_cell_nkv, mask,
-                                    flags & PM355_ATTN_MASK_F16, max_cells, (flags & PM355_ATTN_V_ROWMAJOR) ? 1 : 0,
-                                    (flags & PM355_ATTN_K_Q8_0) ? 1 : 0, (flags & PM355_ATTN_V_Q8_0) ? 1 : 0))
+    pm_attn_tok t = {};
+    t.q = q_rot; t.kc = kc; t.vc = vc; t.pos = d_pos; t.dyn = d_cell_nkv; t.mask = mask; t.out = out; t.scratch = scratch;
+    t.H = H; t.Hkv = Hkv; t.dh = dh; t.n_ctx = n_ctx; t.scale = kq_scale; t.cells = max_cells;
+    t.v_rowmajor = flags & PM355_ATTN_V_ROWMAJOR; t.mask_f16 = flags & PM355_ATTN_MASK_F16;
+    t.k_q8 = flags & PM355_ATTN_K_Q8_0; t.v_q8 = flags & PM355_ATTN_V_Q8_0;
+    if (pm_launch_attn_flash_cached(t, S(st)))
         return fail(PM355_E_UNSUPPORTED, "attn_cached_long: head_dim must be 64/128, <= 16 query heads per KV head, n_ctx % 8 == 0; Q8_0 caches need row-major V");
     HIP_TRY(hipGetLastError());
     return 0;
@@ -535,30 +535,29 @@ int pm355_attn_cached_long_check(int H, int Hkv, int dh, int n_ctx) { return pm_
 int pm355_attn_token(const pm355_attn_token_args * a, const pm355_rope_params * rp, pm355_stream_t st) {
     if (!a || !rp || rp->n_dims % 2 || rp->n_dims > a->head_dim) return fail(PM355_E_SHAPE, "attn_token: n_dims");
     if (!a->d_pos || !a->d_cell_nkv || !a->q || !a->k || !a->v || !a->k_cache || !a->v_cache || !a->out) return fail(PM355_E_SHAPE, "attn_token: null pointer");
-    pm_rope_cfg c;
-    c.n_dims = rp->n_dims; c.mode = rp->mode; c.n_ctx_orig = rp->n_ctx_orig; c.freq_base = rp->freq_base; c.freq_scale = rp->freq_scale;
-    c.ext_factor = rp->ext_factor; c.attn_factor = rp->attn_factor; c.beta_fast = rp->beta_fast; c.beta_slow = rp->beta_slow;
-    pm_rope_params(c);
+    const pm_rope_cfg c = pm_rope_cfg_of(*rp);
+    pm_attn_tok t = {};
+    t.q = a->q; t.k = a->k; t.v = a->v; t.kc = a->k_cache; t.vc = a->v_cache; t.pos = a->d_pos; t.dyn = a->d_cell_nkv; t.mask = a->mask;
+    t.freq_factors = a->freq_factors; t.out = a->out; t.scratch = a->scratch; t.rope = &c; t.cells = a->max_keys;
+    t.H = a->n_head; t.Hkv = a->n_head_kv; t.dh = a->head_dim; t.n_ctx = a->n_ctx; t.scale = a->kq_scale;
+    t.v_rowmajor = a->flags & PM355_ATTN_V_ROWMAJOR; t.mask_f16 = a->flags & PM355_ATTN_MASK_F16;
+    t.k_q8 = a->flags & PM355_ATTN_K_Q8_0; t.v_q8 = a->flags & PM355_ATTN_V_Q8_0;
     (void) hipGetLastError();
-    if (a->flags & (PM355_ATTN_K_Q8_0 | PM355_ATTN_V_Q8_0)) {
+    if (t.k_q8 || t.v_q8) {
         if (!(a->flags & PM355_ATTN_V_ROWMAJOR)) return fail(PM355_E_UNSUPPORTED, "attn_token: a quantized KV cache needs row-major V (flash-attention graphs)");
         if (a->split) {
             // long context: RoPE + quantizing KV store (one small launch), then scores and P.V on the matrix cores over the cached Q8_0 / F16 cells
             // (attn_flash_mfma.hip); max_keys = cells the grid is sized for, scratch zeroed once after its allocation
             if (!a->scratch) return fail(PM355_E_SHAPE, "attn_token(q8_0, long): scratch");
-            float * q_rot = a->scratch + pm_attn_flash_qrot_offset(a->n_head, a->n_head_kv, a->head_dim, a->n_ctx);
-            const int kq = (a->flags & PM355_ATTN_K_Q8_0) ? 1 : 0, vq = (a->flags & PM355_ATTN_V_Q8_0) ? 1 : 0;
-            if (pm_launch_q8_token_prep(a->q, a->k, a->v, a->k_cache, a->v_cache, a->d_pos, a->d_cell_nkv, a->freq_factors, q_rot, a->n_head, a->n_head_kv,
-                                        a->head_dim, a->n_ctx, c, kq, vq, S(st)) ||
-                pm_launch_attn_flash_cached(q_rot, a->k_cache, a->v_cache, nullptr, nullptr, 0, a->out, a->scratch, a->n_head, a->n_head_kv, a->head_dim, a->n_ctx,
-                                            a->kq_scale, S(st), a->d_cell_nkv, a->mask, a->flags & PM355_ATTN_MASK_F16, a->max_keys, 1, kq, vq))
+            pm_attn_tok prep = t, cached = t;
+            prep.out = a->scratch + pm_attn_flash_qrot_offset(a->n_head, a->n_head_kv, a->head_dim, a->n_ctx);
+            cached.q = prep.out; cached.k = cached.v = nullptr; cached.pos = nullptr; cached.freq_factors = nullptr; cached.rope = nullptr;
+            if (pm_launch_q8_token_prep(prep, S(st)) || pm_launch_attn_flash_cached(cached, S(st)))
                 return fail(PM355_E_UNSUPPORTED, "attn_token(q8_0, long): head_dim 64/128, <= 16 query heads per KV head, <= 16 KV heads, n_ctx % 8 == 0");
             HIP_TRY(hipGetLastError());
             return 0;
         }
-        if (pm_launch_attn_q8_token(a->q, a->k, a->v, a->k_cache, a->v_cache, a->d_pos, a->d_cell_nkv, a->mask, a->flags & PM355_ATTN_MASK_F16,
-                                    a->freq_factors, a->out, a->n_head, a->n_head_kv, a->head_dim, a->n_ctx, a->kq_scale, c,
-                                    a->flags & PM355_ATTN_K_Q8_0, a->flags & PM355_ATTN_V_Q8_0, a->max_keys, S(st)))
+        if (pm_launch_attn_q8_token(t, S(st)))
             return fail(PM355_E_UNSUPPORTED, "attn_token(q8_0): head_dim 64/128 and max_keys must fit LDS");
         HIP_TRY(hipGetLastError());
         return 0;
@@ -567,18 +566,13 @@ int pm355_attn_token(const pm355_attn_token_args * a, const pm355_rope_params * 
     if (a->split && !three_launch) {
         // long context, ONE launch: flash-decoding with an in-launch merge (attn_flash.hip); max_keys (> 0) = cells the grid is sized for.
         // The scratch must have been zeroed once after its allocation (ticket words).
-        if (pm_launch_attn_flash(a->q, a->k, a->v, a->k_cache, a->v_cache, a->d_pos, nullptr, 0, a->freq_factors, a->out, a->scratch,
-                                 a->n_head, a->n_head_kv, a->head_dim, a->n_ctx, a->kq_scale, c, S(st), a->d_cell_nkv, a->mask,
-                                 a->flags & PM355_ATTN_V_ROWMAJOR, a->flags & PM355_ATTN_MASK_F16, a->max_keys))
+        if (pm_launch_attn_flash(t, S(st)))
             return fail(PM355_E_UNSUPPORTED, "attn_token(flash): head_dim 64/128, at most 8 query heads per KV head, n_ctx % 8 == 0, scratch required");
     } else if (a->split) {
-        if (pm_launch_attn_split(a->q, a->k, a->v, a->k_cache, a->v_cache, a->d_pos, nullptr, 0, a->freq_factors, a->out, a->scratch,
-                                 a->n_head, a->n_head_kv, a->head_dim, a->n_ctx, a->kq_scale, &c, S(st), a->d_cell_nkv, a->mask,
-                                 a->flags & PM355_ATTN_V_ROWMAJOR, a->flags & PM355_ATTN_MASK_F16))
+        t.cells = 0;                                  // (the three-launch form has nothing max_keys would size)
+        if (pm_launch_attn_split(t, S(st)))
             return fail(PM355_E_UNSUPPORTED, "attn_token(split): head_dim 64/128, at most 8 query heads per KV head, n_ctx % 8 == 0, scratch required");
-    } else if (pm_launch_attn_rope_fused(a->q, a->k, a->v, a->k_cache, a->v_cache, a->d_pos, nullptr, 0, a->freq_factors, a->out,
-                                         a->n_head, a->n_head_kv, a->head_dim, a->n_ctx, a->kq_scale, c, S(st), a->d_cell_nkv, a->mask, a->max_keys,
-                                         a->flags & PM355_ATTN_V_ROWMAJOR, a->flags & PM355_ATTN_MASK_F16))
+    } else if (pm_launch_attn_rope_fused(t, S(st)))
         return fail(PM355_E_UNSUPPORTED, "attn_token: head_dim must be 64/128/256, n_ctx % 8 == 0 and max_keys fit LDS");
     HIP_TRY(hipGetLastError());
     return 0;

@@ -369,6 +369,18 @@ int run_head(pm355_model * m, const float * x_row, float * d_logits, int32_t * d
     return 0;
 }
 
+// keys the per-head attention kernels size their LDS score buffer for: with the long-context forms available they only ever see fewer than
+// split_min cells (long contexts stay launchable); 0: n_ctx
+int head_score_keys(const pm355_model * m) { return (m->split_scratch && m->split_min + 8 < m->hp.n_ctx) ? m->split_min + 8 : 0; }
+// the fields every attention launch of the engine shares, over layer L's caches; the caller adds what its form needs
+pm_attn_tok attn_args(const pm355_model * m, const Layer & L, int n_tok, long seq_stride) {
+    const pm355_hparams & hp = m->hp;
+    pm_attn_tok a = {};
+    a.q = m->q; a.kc = L.kc; a.vc = L.vc; a.out = m->att; a.pos = m->d_pos; a.seq = m->d_ctl; a.seq_stride = seq_stride; a.n_tok = n_tok;
+    a.H = hp.n_head; a.Hkv = hp.n_head_kv; a.dh = hp.head_dim; a.n_ctx = hp.n_ctx; a.scale = 1.0f / sqrtf((float) hp.head_dim);
+    return a;
+}
+
 // The single-token layer stack as ONE persistent launch: the same launches run_layers_fused issues, appended as phases (decode_engine.hip).
 // nullptr: this window is not served (types, shapes, streaming, long-context regime) - the caller takes the five-launch path.
 // may_build = false (the stream is being captured: no allocation, no synchronous copy): only a plan that exists already is returned.
@@ -393,7 +405,7 @@ pm355_model::EnginePlan * engine_plan_for(pm355_model * m, const float * cur, fl
         (void) hipGetLastError();
         pm_eng_plan_free(pl); (void) hipFree(act); m->eng_refused = true; return nullptr;
     };
-    const int max_keys = (m->split_scratch && m->split_min + 8 < hp.n_ctx) ? m->split_min + 8 : hp.n_ctx;
+    const int max_keys = head_score_keys(m) ? head_score_keys(m) : hp.n_ctx;
     double * ss_in0 = (double *) ((char *) act + per_bytes * (size_t) nl);
     const double * ss_prev = ss_in0; int n_prev = 1;          // partials of the sum of squares of `cur`
     auto job = [](pm_gemv_fused & f, int j, const Tensor & w, const Tensor * w2, float * y, const float * bias, const float * resid) {
@@ -469,6 +481,13 @@ int attn_regime(const pm355_model * m) {
     return (int) (b > m->hp.n_ctx ? m->hp.n_ctx : b);
 }
 
+// which form the single-token attention of a step takes (the same for every layer of the window)
+enum class DecodeAttn { flash_cached, flash, split, tail, cached, rope_fused };
+DecodeAttn decode_attn_path(const pm355_model * m, bool epi, bool tail) {
+    if (m->long_ctx) return epi ? DecodeAttn::flash_cached : m->use_flash ? DecodeAttn::flash : DecodeAttn::split;
+    return !epi ? DecodeAttn::rope_fused : tail ? DecodeAttn::tail : DecodeAttn::cached;
+}
+
 // the single-token layer sequence (5 launches per layer)
 // *n_ss_end: number of partials the LAST layer's ffn_down left in m->ss + 256 for the sum of squares of the window's output row (0: none)
 int run_layers_fused(pm355_model * m, const float * cur, float * d_x_out, const float ** cur_out, hipStream_t st, int * n_ss_end = nullptr) {
@@ -484,6 +503,8 @@ int run_layers_fused(pm355_model * m, const float * cur, float * d_x_out, const 
     bool tail = epi && !m->long_ctx && m->attn_tail && m->att_tk && Hkv <= 64;
     double * ss_wo = (m->use_ss && m->ss) ? m->ss : nullptr, * ss_dn = ss_wo ? m->ss + 256 : nullptr;
     int n_wo = 0, n_dn = 0;                           // partials the previous wo / ffn_down launch left (0: the consumer reduces the row itself)
+    DecodeAttn path = DecodeAttn::rope_fused;
+    pm_attn_tok a = {};                               // the step's attention arguments: filled once the first layer has settled the path, then only kc / vc change
     for (int il = m->lo; il < m->hi; ++il) {
         Layer Lv = layer_acquire(m, il, st); Layer & L = Lv;
         float * q = m->q, * k = m->k, * v = m->v, * att = m->att, * hbuf = m->h;
@@ -499,7 +520,7 @@ int run_layers_fused(pm355_model * m, const float * cur, float * d_x_out, const 
             bool qkv_done = false;
             if (tail) {
                 qe.att_out = att; qe.att_ticket = m->att_tk; qe.att_err = (int *) (m->att_tk + 64); qe.kq_scale = kq_scale; qe.n_head = H;
-                qe.att_max_keys = (m->split_scratch && m->split_min + 8 < hp.n_ctx) ? m->split_min + 8 : 0;
+                qe.att_max_keys = head_score_keys(m);
                 qkv_done = gemv_f32(m, ws, nullptr, ys, bs, nullptr, 3, cur, nw, st, &qe, nullptr, nullptr, ss_dn, n_dn) == 0;
                 if (!qkv_done) {
                     if (il != m->lo) return seterr(m, PM355_E_UNSUPPORTED, "decode: attention tail served for some layers only");
@@ -519,34 +540,29 @@ int run_layers_fused(pm355_model * m, const float * cur, float * d_x_out, const 
                     if (gemv_f32(m, ws + j, nullptr, ys + j, bs + j, nullptr, 1, cur, nw, st)) return seterr(m, PM355_E_UNSUPPORTED, "decode: fused qkv gemv");
             }
         }
-        const long kvs = m->n_seq > 1 ? (long) hp.n_ctx * Hkv * dh : 0;     // one slab: the kernels may address the cache before the sequence id arrives
-        if (m->long_ctx && epi) {
-            // long context, cells complete: scores and P.V on the matrix cores, keys split over workgroups, in-launch merge (attn_flash_mfma.hip)
-            if (pm_launch_attn_flash_cached(q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, att, m->split_scratch, H, Hkv, dh, hp.n_ctx, kq_scale, st,
-                                            nullptr, nullptr, 0, m->flash_cells))
-                return seterr(m, PM355_E_RANGE, "decode: matrix-core flash-decoding attention unsupported for this shape");
-        } else if (m->long_ctx && m->use_flash) {
-            // long context: keys split over workgroups, rope + KV store + online softmax + in-launch merge in ONE launch (attn_flash.hip)
-            if (pm_launch_attn_flash(q, k, v, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, (const float *) m->rope_freqs.d, att, m->split_scratch,
-                                     H, Hkv, dh, hp.n_ctx, kq_scale, m->rope, st, nullptr, nullptr, 0, 0, m->flash_cells))
-                return seterr(m, PM355_E_RANGE, "decode: flash-decoding attention unsupported for this shape");
-        } else if (m->long_ctx) {
-            // (PM355_ATTN_FLASH=0) the three-launch form: scores, probabilities + partial P.V, combine (attn_split.hip)
-            if (pm_launch_attn_split(q, k, v, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, (const float *) m->rope_freqs.d, att, m->split_scratch,
-                                     H, Hkv, dh, hp.n_ctx, kq_scale, &m->rope, st))
-                return seterr(m, PM355_E_RANGE, "decode: split attention unsupported for this shape");
-        } else if (epi && tail) {
-            // (the attention ran in the tail of the wq | wk | wv launch)
-        } else if (epi) {
-            if (pm_launch_attn_cached(q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, att, H, Hkv, dh, hp.n_ctx, kq_scale, st, nullptr, nullptr,
-                                      (m->split_scratch && m->split_min + 8 < hp.n_ctx) ? m->split_min + 8 : 0))
-                return seterr(m, PM355_E_RANGE, "decode: cached attention unsupported for this head_dim / n_ctx");
-        } else if (pm_launch_attn_rope_fused(q, k, v, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, (const float *) m->rope_freqs.d,
-                                             att, H, Hkv, dh, hp.n_ctx, kq_scale, m->rope, st, nullptr, nullptr,
-                                             // with the split path available this kernel only ever sees < split_min cells: its LDS
-                                             // score buffer is sized for that, not for n_ctx (long contexts stay launchable)
-                                             (m->split_scratch && m->split_min + 8 < hp.n_ctx) ? m->split_min + 8 : 0))
-            return seterr(m, PM355_E_RANGE, "decode: fused attention unsupported for this head_dim / n_ctx");
+        if (il == m->lo) {                             // the first layer's wq | wk | wv launch has settled epi and tail
+            path = decode_attn_path(m, epi, tail);
+            a = attn_args(m, L, 1, m->n_seq > 1 ? (long) hp.n_ctx * Hkv * dh : 0);      // one slab: the kernels may address the cache before the sequence id arrives
+            if (path == DecodeAttn::flash || path == DecodeAttn::split || path == DecodeAttn::rope_fused) {      // raw projections: rope + KV store in the attention launch
+                a.k = k; a.v = v; a.freq_factors = (const float *) m->rope_freqs.d; a.rope = &m->rope;
+            }
+            // the flash forms' grid is sized for flash_cells; the per-head kernels' LDS score buffer for head_score_keys, not for n_ctx
+            if (m->long_ctx) { a.scratch = m->split_scratch; a.cells = path == DecodeAttn::split ? 0 : m->flash_cells; } else a.cells = head_score_keys(m);
+        }
+        a.kc = L.kc; a.vc = L.vc;
+        int rc = 0; const char * why = nullptr;
+        switch (path) {
+        // long context, cells complete: scores and P.V on the matrix cores, keys split over workgroups, in-launch merge (attn_flash_mfma.hip)
+        case DecodeAttn::flash_cached: rc = pm_launch_attn_flash_cached(a, st); why = "decode: matrix-core flash-decoding attention unsupported for this shape"; break;
+        // long context: keys split over workgroups, rope + KV store + online softmax + in-launch merge in ONE launch (attn_flash.hip)
+        case DecodeAttn::flash: rc = pm_launch_attn_flash(a, st); why = "decode: flash-decoding attention unsupported for this shape"; break;
+        // (PM355_ATTN_FLASH=0) the three-launch form: scores, probabilities + partial P.V, combine (attn_split.hip)
+        case DecodeAttn::split: rc = pm_launch_attn_split(a, st); why = "decode: split attention unsupported for this shape"; break;
+        case DecodeAttn::tail: break;                  // (the attention ran in the tail of the wq | wk | wv launch)
+        case DecodeAttn::cached: rc = pm_launch_attn_cached(a, st); why = "decode: cached attention unsupported for this head_dim / n_ctx"; break;
+        case DecodeAttn::rope_fused: rc = pm_launch_attn_rope_fused(a, st); why = "decode: fused attention unsupported for this head_dim / n_ctx"; break;
+        }
+        if (rc) return seterr(m, PM355_E_RANGE, why);
         {
             const Tensor * w[1] = {&L.t[PM355_T_WO]}; float * y[1] = {x_mid}; const float * r[1] = {cur};
             if (gemv_f32(m, w, nullptr, y, nullptr, r, 1, att, nullptr, st, nullptr, ss_wo, &n_wo)) return seterr(m, PM355_E_UNSUPPORTED, "decode: fused wo gemv");
@@ -623,7 +639,7 @@ int layer_prompt_i8(pm355_model * m, const Layer & L, int T, const float * cur, 
     pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kvs,
                             (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st);
     if (pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st) &&
-        pm_launch_attn_decode(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st))
+        pm_launch_attn_decode(attn_args(m, L, T, kvs), st))
         return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
     pm_launch_quantize_q8k(m->att, m->aq_k, H * dh, T, st, TB(H * dh));
     if (GI(L.t[PM355_T_WO], x_mid, nullptr, cur)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: wo mat-mul");
@@ -663,8 +679,7 @@ int layer_prompt_f16(pm355_model * m, const Layer & L, int T, const float * cur,
     bool att_h = true;
     if (pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, nullptr, T, H, Hkv, dh, hp.n_ctx, kq_scale, st, nullptr, 0, 0, 0, 0, m->att)) {
         att_h = false;
-        if (pm_launch_attn_decode(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st))
-            return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
+        if (pm_launch_attn_decode(attn_args(m, L, T, kvs), st)) return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
     }
     const Tensor & wo = L.t[PM355_T_WO];
     if (att_h ? G(wo, m->att, x_mid, nullptr, nullptr, cur)
@@ -746,9 +761,9 @@ int small_attention(pm355_model * m, const Layer & L, int T, bool rope_done, con
     // (a shape attn_cached refuses - head_dim other than 64 / 128 / 256, scores beyond 150 KiB of LDS - falls back to attn_decode, which rounds q to
     //  F16 itself: the pre-rounded rows give it the same bits as raw ones, tests/test_gpu_ops.py::test_small_batch_attention_fallback_...)
     // (from SMALL_ATTN_MFMA_MIN tokens on: the prompt path's matrix-core kernel - 12 us per layer at 32 tokens against 26 for 2048 small workgroups)
+    const pm_attn_tok at = attn_args(m, L, T, kv_stride);
     if (!(T >= SMALL_ATTN_MFMA_MIN && pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st) == 0) &&
-        pm_launch_attn_cached(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, H, Hkv, dh, hp.n_ctx, kq_scale, st, nullptr, nullptr, 0, 0, 0, T) &&
-        pm_launch_attn_decode(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st))
+        pm_launch_attn_cached(at, st) && pm_launch_attn_decode(at, st))
         return seterr(m, PM355_E_RANGE, "decode: n_ctx too large for the decode-attention kernel");
     const Tensor * wo[1] = {&L.t[PM355_T_WO]};
     const ActQ a = quantize_for(m, m->att, H * dh, T, wo, 1, st);

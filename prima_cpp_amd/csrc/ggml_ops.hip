@@ -439,10 +439,7 @@ int pm355_op_rope(const pm355_tensor * a, const int32_t * d_pos, const float * f
                   const pm355_rope_params * rp, pm355_stream_t st) {
     if ((a->type != PM_F32 && a->type != PM_F16) || dst->type != a->type || !rp || rp->n_dims % 2 || rp->n_dims > a->ne[0] || a->ne[0] % 2) return PM355_E_UNSUPPORTED;
     if (rp->mode & ~2) return PM355_E_UNSUPPORTED;                   // only NORM (0) and NEOX (2)
-    pm_rope_cfg c;
-    c.n_dims = rp->n_dims; c.mode = rp->mode; c.n_ctx_orig = rp->n_ctx_orig; c.freq_base = rp->freq_base; c.freq_scale = rp->freq_scale;
-    c.ext_factor = rp->ext_factor; c.attn_factor = rp->attn_factor; c.beta_fast = rp->beta_fast; c.beta_slow = rp->beta_slow;
-    pm_rope_params(c);
+    const pm_rope_cfg c = pm_rope_cfg_of(*rp);
     RopeG r = {c.n_dims, c.mode, c.theta_scale, c.freq_scale, c.ext_factor, c.attn_factor, c.corr0, c.corr1};
     (void) hipGetLastError();
     if (a->type == PM_F16)

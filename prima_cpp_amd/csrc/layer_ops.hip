@@ -319,50 +319,48 @@ void pm_rope_params(pm_rope_cfg & c) {
     c.corr0 = fmaxf(0, floorf(corr_dim(c.beta_fast)));
     c.corr1 = fminf((float) (c.n_dims - 1), ceilf(corr_dim(c.beta_slow)));
 }
+pm_rope_cfg pm_rope_cfg_of(const pm355_rope_params & rp) {
+    pm_rope_cfg c;
+    c.n_dims = rp.n_dims; c.mode = rp.mode; c.n_ctx_orig = rp.n_ctx_orig; c.freq_base = rp.freq_base; c.freq_scale = rp.freq_scale;
+    c.ext_factor = rp.ext_factor; c.attn_factor = rp.attn_factor; c.beta_fast = rp.beta_fast; c.beta_slow = rp.beta_slow;
+    pm_rope_params(c);
+    return c;
+}
 
 void pm_launch_rope_kv_store(const float * q, const float * k, const float * v, float * q_out, float * k_out_f32,
                              void * kc, void * vc, const int32_t * pos0, const int32_t * seq, long seq_stride,
                              const float * freq_factors,
                              int n_tok, int H, int Hkv, int dh, int n_ctx, const pm_rope_cfg & c, hipStream_t st, int round_q) {
-    RopeP r;
-    r.n_dims = c.n_dims; r.mode = c.mode; r.n_ctx_orig = c.n_ctx_orig; r.theta_scale = c.theta_scale;
-    r.freq_scale = c.freq_scale; r.ext_factor = c.ext_factor; r.attn_factor = c.attn_factor; r.corr0 = c.corr0; r.corr1 = c.corr1;
     hipLaunchKernelGGL(rope_kv_store_kernel, dim3(H + Hkv, n_tok), dim3(64), 0, st,
-                       q, k, v, q_out, k_out_f32, (uint16_t *) kc, (uint16_t *) vc, pos0, seq, seq_stride, freq_factors, H, Hkv, dh, n_ctx, r, round_q);
+                       q, k, v, q_out, k_out_f32, (uint16_t *) kc, (uint16_t *) vc, pos0, seq, seq_stride, freq_factors, H, Hkv, dh, n_ctx, rope_p(c), round_q);
 }
 
-int pm_launch_attn_decode(const float * q, const void * kc, const void * vc, const int32_t * pos0,
-                          const int32_t * seq, long seq_stride, float * out,
-                          int n_tok, int H, int Hkv, int dh, int n_ctx, float scale, hipStream_t st) {
+int pm_launch_attn_decode(const pm_attn_tok & a, hipStream_t st) {
+    const int dh = a.dh, n_ctx = a.n_ctx;
     const size_t lds = (size_t) (dh + n_ctx) * 4;
-    if (lds > 150 * 1024 || dh % 8 || n_ctx % 8) return -1;
+    if (lds > PM_ATTN_LDS_MAX || dh % 8 || n_ctx % 8 || a.rope || a.dyn || a.mask || a.v_rowmajor || a.k_q8 || a.v_q8 || a.cells) return -1;
     if (lds > 48 * 1024) {
         static bool set[16] = {};
         const int dv = pm_cur_dev();
         if (!set[dv]) { (void) hipFuncSetAttribute((const void *) attn_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); set[dv] = true; }
     }
-    hipLaunchKernelGGL(attn_decode_kernel, dim3(H, n_tok), dim3(256), lds, st,
-                       q, (const uint16_t *) kc, (const uint16_t *) vc, pos0, seq, seq_stride, out, H, Hkv, dh, n_ctx, scale);
+    hipLaunchKernelGGL(attn_decode_kernel, dim3(a.H, a.n_tok), dim3(256), lds, st,
+                       a.q, (const uint16_t *) a.kc, (const uint16_t *) a.vc, a.pos, a.seq, a.seq_stride, a.out, a.H, a.Hkv, dh, n_ctx, a.scale);
     return 0;
 }
 
-int pm_launch_attn_rope_fused(const float * q, const float * k, const float * v, void * kc, void * vc,
-                               const int32_t * pos0, const int32_t * seq, long seq_stride, const float * freq_factors,
-                               float * out, int H, int Hkv, int dh, int n_ctx, float scale, const pm_rope_cfg & c, hipStream_t st,
-                               const int32_t * dyn, const void * mask, int max_keys, int v_rowmajor, int mask_f16) {
-    if ((dh != 64 && dh != 128 && dh != 256) || n_ctx % 8) return -1;
-    const size_t lds = (size_t) (4 * dh + (v_rowmajor ? 2048 : 256) + (max_keys > 0 ? ((max_keys + 7) & ~7) : n_ctx) + 8) * 4;
-    if (lds > 150 * 1024) return -1;
-    RopeP r;
-    r.n_dims = c.n_dims; r.mode = c.mode; r.n_ctx_orig = c.n_ctx_orig; r.theta_scale = c.theta_scale;
-    r.freq_scale = c.freq_scale; r.ext_factor = c.ext_factor; r.attn_factor = c.attn_factor; r.corr0 = c.corr0; r.corr1 = c.corr1;
+int pm_launch_attn_rope_fused(const pm_attn_tok & t, hipStream_t st) {
+    const int dh = t.dh;
+    if ((dh != 64 && dh != 128 && dh != 256) || t.n_ctx % 8) return -1;
+    const size_t lds = pm_attn_head_lds(dh, t.n_ctx, t.v_rowmajor, t.cells);
+    if (lds > PM_ATTN_LDS_MAX || !t.rope || t.k_q8 || t.v_q8 || t.n_tok != 1) return -1;
     auto launch = [&](auto kern) {
         if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        AttnP a = {q, k, v, (uint16_t *) kc, (uint16_t *) vc, pos0, seq, seq_stride, freq_factors, out, H, Hkv, n_ctx, scale, r, dyn,
-                   (const float *) mask, mask_f16, pm_ts_next_slot()};
-        hipLaunchKernelGGL(kern, dim3(H), dim3(256), lds, st, a);
+        AttnP a = {t.q, t.k, t.v, (uint16_t *) t.kc, (uint16_t *) t.vc, t.pos, t.seq, t.seq_stride, t.freq_factors, t.out, t.H, t.Hkv, t.n_ctx, t.scale,
+                   rope_p(*t.rope), t.dyn, (const float *) t.mask, t.mask_f16, pm_ts_next_slot()};
+        hipLaunchKernelGGL(kern, dim3(t.H), dim3(256), lds, st, a);
     };
-    if (v_rowmajor) {
+    if (t.v_rowmajor) {
         if (dh == 64) launch(attn_rope_fused_kernel<64, 1>);
         else if (dh == 128) launch(attn_rope_fused_kernel<128, 1>);
         else launch(attn_rope_fused_kernel<256, 1>);

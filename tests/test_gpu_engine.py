@@ -235,6 +235,54 @@ def test_long_context_split_attention_path(E, monkeypatch, flash, n_head, n_embd
         assert _nmse(h1, h0) < 1e-4 and _nmse(l1, l0) < 1e-3        # the whole-stack bound used against the reference itself
 
 
+@pytest.mark.parametrize("flash,n_head,n_embd,n_head_kv", [("1", 4, 256, 2), ("0", 4, 256, 2), ("1", 8, 1024, 4)])
+def test_long_context_attention_reads_its_own_sequence_slab(E, monkeypatch, flash, n_head, n_embd, n_head_kv):
+    """Two sequences in one window, beyond PM355_ATTN_SPLIT_MIN: the long-context forms (attn_flash.hip, attn_split.hip with PM355_ATTN_FLASH=0, and
+    - n_embd 1024: the QKV epilogue is served - attn_flash_mfma.hip, head_dim 128) must take the position and the KV slab of the CURRENT sequence.
+    Sequence 0 is a decoy: other tokens, 20 positions ahead, stepped in turn with sequence 1. Sequence 1 must give what a window with ONE sequence
+    gives for the same tokens through the same forms, under the bound of test_long_context_split_attention_path (a dropped sequence pointer or
+    stride reads the decoy's slab: an error of order 1). n_ctx 1088: no power of two, no multiple of 1024.
+    (The reference is the same form on purpose. Against the one-workgroup-per-head kernel - PM355_ATTN_SPLIT_MIN=100000, what that neighbour compares
+    at n_embd >= 512 - this n_embd 256 model measures, before and after the argument block alike: attn_flash.hip nmse 0 up to position 39, then hidden
+    1.02e-4 / logits 1.62e-4 at position 40, the first long-context step; attn_split.hip and attn_flash_mfma.hip stay under 1e-4 / 1e-3 throughout.
+    That is the two kernels' summation order on a small model, not the sequence wiring.)"""
+    torch = E.torch
+    rng = np.random.default_rng(79)
+    monkeypatch.setenv("PM355_ATTN_FLASH", flash)
+    d = tiny_model(rng, arch=0, n_layer=2, n_embd=n_embd, n_head=n_head, n_head_kv=n_head_kv, n_ff=512, n_vocab=320, n_ctx=1088, rope_freqs=True)
+    toks = rng.integers(0, d.n_vocab, 56).astype(np.int32)
+    decoy = rng.integers(0, d.n_vocab, 56).astype(np.int32)
+    at = (0, 39, 40, 41, 47, 55)
+    x_out = torch.empty((1, d.n_embd), dtype=torch.float32, device="cuda")
+    lg = torch.empty(d.n_vocab, dtype=torch.float32, device="cuda")
+    tok = torch.zeros(1, dtype=torch.int32, device="cuda")
+    res = []
+    monkeypatch.setenv("PM355_ATTN_SPLIT_MIN", "40")
+    for n_seq in (1, 2):
+        w = E.Window(_hp(d), n_ctx=1088)
+        w.load_desc(d); w.finalize(1, n_seq=n_seq)
+        w.kv_clear()
+        out = []
+        if n_seq == 2:
+            w.set_seq_pos(0, 20); w.set_seq_pos(1, 0); w.set_seq(0)
+        else:
+            w.set_pos(0)
+        for i, t in enumerate(toks):
+            if n_seq == 2:
+                tok[0] = int(decoy[i])
+                w.step_ex(token=tok, x_out=x_out, logits=lg, advance=1, rotate=1, use_graph=i % 2 == 0)      # sequence 0, then on to sequence 1
+            tok[0] = int(t)
+            w.step_ex(token=tok, x_out=x_out, logits=lg, advance=1, rotate=n_seq - 1, use_graph=i % 2 == 0)
+            if i in at:
+                torch.cuda.synchronize()
+                out.append((x_out.cpu().numpy().copy(), lg.cpu().numpy().copy()))
+        res.append(out)
+        w.close()
+    for i, ((h0, l0), (h1, l1)) in zip(at, zip(*res)):
+        print(f"position {i}: nmse hidden {_nmse(h1, h0):.3g} logits {_nmse(l1, l0):.3g}")
+        assert _nmse(h1, h0) < 1e-4 and _nmse(l1, l0) < 1e-3
+
+
 def test_step_refuses_to_write_past_the_kv_slab(E):
     """pm355_model_step_ex / set_seq_pos must bound the position by n_ctx (llama_decode returns an error when no KV
     cell is left, src/llama.cpp:18445); a failed step must not move the host mirror of the device counters."""

@@ -1251,3 +1251,103 @@ def test_small_batch_attention_fallback_is_indifferent_to_the_pre_rounded_query(
     raw = P.attn_decode(q, kc, vc, pos0, H, Hkv, dh, n_ctx, scale)
     rounded = P.attn_decode(q.half().float(), kc, vc, pos0, H, Hkv, dh, n_ctx, scale)
     assert torch.equal(raw, rounded)
+
+
+@pytest.mark.parametrize("dh,flags,masked", [(64, 0, False), (128, 0, False), (64, 1, True), (64, 2, True)])
+def test_cached_attention_score_buffer_sized_for_max_keys_and_each_flag_on_its_own(P, dh, flags, masked):
+    """pm355_attn_cached on a cache of 40000 cells: n_ctx scores would not fit in LDS, so the launch exists only because max_keys (64) sizes the
+    score buffer. flags 1 = row-major V with an F32 mask, 2 = F16 mask with the transposed V (each flag without the other: a launcher that
+    swapped them reads V in the wrong layout). Masked cases: ggml-graph mode, every third cell hidden and filled with decoy values of 50.
+    Against float64 softmax attention under the bound of test_qkv_epilogue_and_cached_attention_equal_the_fused_attention_path."""
+    torch = P.torch
+    rng = np.random.default_rng(97 + dh + flags)
+    H, Hkv, n_ctx, n_kv = 4, 2, 40000, 48
+    Nkv = Hkv * dh
+    q = rng.normal(0, 1, (H, dh)).astype(np.float16).astype(np.float32)
+    K = rng.normal(0, 1, (n_kv, Nkv)).astype(np.float16)
+    V = rng.normal(0, 1, (n_kv, Nkv)).astype(np.float16)
+    hidden = (np.arange(n_kv) % 3 == 1) if masked else np.zeros(n_kv, dtype=bool)
+    K[hidden] = 50; V[hidden] = 50
+    kc = torch.zeros((n_ctx, Nkv), dtype=torch.float16, device="cuda")
+    kc[:n_kv] = torch.from_numpy(K).cuda()
+    if flags & 1:
+        vc = torch.zeros((n_ctx, Nkv), dtype=torch.float16, device="cuda")
+        vc[:n_kv] = torch.from_numpy(V).cuda()
+    else:
+        vc = torch.zeros((Nkv, n_ctx), dtype=torch.float16, device="cuda")
+        vc[:, :n_kv] = torch.from_numpy(np.ascontiguousarray(V.T)).cuda()
+    scale = 1.0 / np.sqrt(dh)
+    qd = torch.from_numpy(q.reshape(1, -1)).cuda()
+    if masked:
+        m = np.where(hidden, -np.inf, 0.0).astype(np.float16 if flags & 2 else np.float32)
+        dyn = torch.tensor([n_kv - 1, n_kv], dtype=torch.int32, device="cuda")
+        out = P.attn_cached(qd, kc.view(torch.int16), vc.view(torch.int16), None, H, Hkv, dh, n_ctx, scale, cell_nkv=dyn, mask=torch.from_numpy(m).cuda(),
+                            max_keys=64, flags=flags)
+    else:
+        pd = torch.tensor([n_kv - 1], dtype=torch.int32, device="cuda")
+        out = P.attn_cached(qd, kc.view(torch.int16), vc.view(torch.int16), pd, H, Hkv, dh, n_ctx, scale, max_keys=64)
+    got = out.cpu().numpy().reshape(H, dh).astype(np.float64)
+    want = np.zeros((H, dh))
+    for h in range(H):
+        hk = h // (H // Hkv)
+        s = K[:, hk * dh:(hk + 1) * dh].astype(np.float64) @ q[h].astype(np.float64) * scale
+        s[hidden] = -np.inf
+        p = np.exp(s - s.max()); p /= p.sum()
+        want[h] = p @ V[:, hk * dh:(hk + 1) * dh].astype(np.float64)
+    err = np.abs(got - want).max()
+    print(f"dh {dh} flags {flags}: max |d out| {err:.3g}, max |out| {np.abs(want).max():.3g}")
+    assert err <= 3e-3 * max(1.0, np.abs(want).max())
+
+
+@pytest.mark.parametrize("flags", [0, 1, 2])
+@pytest.mark.parametrize("form", ["rope_fused", "long"])
+def test_attn_token_f16_caches_cell_mask_and_each_layout_flag_alone(P, form, flags):
+    """pm355_attn_token on F16 caches in ggml-graph mode, one workgroup per head (attn_rope_fused_kernel) and the long-context form (scratch given:
+    attn_flash.hip, or attn_split.hip under PM355_ATTN_FLASH=0). The token sits in cache cell 47 while its RoPE position is 0 (the rotation is then
+    the identity, so the stored K row is F16(k) exactly): a launcher that dropped dyn, or took the position for the cell, stores and attends
+    elsewhere. Every third cell is hidden by the mask and holds decoy values of 50. flags 1 = row-major V with an F32 mask, 2 = F16 mask with the
+    transposed V: each flag without the other. The one-workgroup form runs on a cache of 40000 cells, launchable only because max_keys (64) sizes
+    its score buffer. Against the float64 restatement and bound of test_attn_decode_vs_oracle (p rounded to F16 where the reference graph does)."""
+    torch = P.torch
+    rng = np.random.default_rng(123 + flags)
+    H, Hkv, dh, n_kv = 4, 2, 64, 48
+    Nkv, cell = Hkv * dh, n_kv - 1
+    n_ctx = 40000 if form == "rope_fused" else 1088
+    q = rng.normal(0, 1, (H, dh)).astype(np.float32)
+    k = rng.normal(0, 1, (1, Nkv)).astype(np.float32)
+    v = rng.normal(0, 1, (1, Nkv)).astype(np.float32)
+    K = rng.normal(0, 1, (n_kv, Nkv)).astype(np.float16)
+    V = rng.normal(0, 1, (n_kv, Nkv)).astype(np.float16)
+    hidden = np.arange(n_kv) % 3 == 1
+    K[hidden] = 50; V[hidden] = 50
+    K[cell] = 0; V[cell] = 0                                       # the launch writes this cell
+    kc = torch.zeros((n_ctx, Nkv), dtype=torch.float16, device="cuda")
+    kc[:n_kv] = torch.from_numpy(K).cuda()
+    if flags & 1:
+        vc = torch.zeros((n_ctx, Nkv), dtype=torch.float16, device="cuda")
+        vc[:n_kv] = torch.from_numpy(V).cuda()
+    else:
+        vc = torch.zeros((Nkv, n_ctx), dtype=torch.float16, device="cuda")
+        vc[:, :n_kv] = torch.from_numpy(np.ascontiguousarray(V.T)).cuda()
+    mask = torch.from_numpy(np.where(hidden, -np.inf, 0.0).astype(np.float16 if flags & 2 else np.float32)).cuda()
+    pos = torch.tensor([0], dtype=torch.int32, device="cuda")
+    dyn = torch.tensor([cell, n_kv], dtype=torch.int32, device="cuda")
+    scale = 1.0 / np.sqrt(dh)
+    kw = dict(scratch=P.attn_split_scratch(H, dh, n_ctx), max_keys=128) if form == "long" else dict(max_keys=64)
+    out = P.attn_token(_dev(P, q.reshape(1, -1)), _dev(P, k), _dev(P, v), kc.view(torch.int16), vc.view(torch.int16), pos, dyn, H, Hkv, dh, n_ctx, scale,
+                       flags=flags, mask=mask, **kw).cpu().numpy().reshape(H, dh)
+    K[cell] = k[0].astype(np.float16); V[cell] = v[0].astype(np.float16)
+    assert np.array_equal(kc[:n_kv].cpu().numpy().view(np.uint16), K.view(np.uint16))
+    v_got = vc[:n_kv].cpu().numpy() if flags & 1 else vc[:, :n_kv].cpu().numpy().T
+    assert np.array_equal(np.ascontiguousarray(v_got).view(np.uint16), V.view(np.uint16))
+    qh = q.astype(np.float16).astype(np.float64)
+    for h in range(H):
+        hk = h // (H // Hkv)
+        s = (K[:, hk * dh:(hk + 1) * dh].astype(np.float64) @ qh[h]).astype(np.float32) * np.float32(scale)
+        s[hidden] = -np.inf
+        e = np.exp((s - s.max()).astype(np.float32)).astype(np.float32)
+        p = e * np.float32(1.0 / e.astype(np.float64).sum())
+        p = (p if flags & 1 else p.astype(np.float16)).astype(np.float64)
+        want = p @ V[:, hk * dh:(hk + 1) * dh].astype(np.float64)
+        print(f"{form} flags {flags} head {h}: max |d out| {np.abs(out[h] - want).max():.3g}, max |out| {np.abs(want).max():.3g}")
+        assert np.abs(out[h] - want).max() <= 2e-3 * np.abs(want).max() + 1e-4, h
