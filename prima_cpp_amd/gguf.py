@@ -160,10 +160,21 @@ class GGUFFile:
 ARCH_NAMES = {0: "llama", 1: "qwen2"}
 
 
-def model_kv(arch, n_layer, n_embd, n_head, n_head_kv, n_ff, n_vocab, n_ctx_train, rms_eps, rope_freq_base, name="synthetic"):
-    """Metadata of llm_load_hparams (src/llama.cpp:5823-5960) for a dense llama / qwen2 model without a vocabulary."""
+def model_kv(arch, n_layer, n_embd, n_head, n_head_kv, n_ff, n_vocab, n_ctx_train, rms_eps, rope_freq_base, name="synthetic", rope_scaling=None,
+             rope_dimension_count=None):
+    """Metadata of llm_load_hparams (src/llama.cpp:5823-5960) for a dense llama / qwen2 model without a vocabulary.
+    rope_scaling: optional dict(type="linear" | "yarn" | "none", factor=float, original_context_length=int) -> the {arch}.rope.scaling.* keys
+    (:5883-5896); rope_dimension_count overrides {arch}.rope.dimension_count (n_rot; the llama arch refuses anything but the head size, :5921)."""
     a = ARCH_NAMES[arch]
-    return {
+    extra = {}
+    if rope_scaling:
+        if "type" in rope_scaling:
+            extra[f"{a}.rope.scaling.type"] = (T_STR, rope_scaling["type"])
+        if "factor" in rope_scaling:
+            extra[f"{a}.rope.scaling.factor"] = (T_F32, float(rope_scaling["factor"]))
+        if "original_context_length" in rope_scaling:
+            extra[f"{a}.rope.scaling.original_context_length"] = (T_U32, int(rope_scaling["original_context_length"]))
+    kv = {
         "general.architecture": (T_STR, a),
         "general.name": (T_STR, name),
         f"{a}.context_length": (T_U32, n_ctx_train),
@@ -174,10 +185,12 @@ def model_kv(arch, n_layer, n_embd, n_head, n_head_kv, n_ff, n_vocab, n_ctx_trai
         f"{a}.attention.head_count_kv": (T_U32, n_head_kv),
         f"{a}.attention.layer_norm_rms_epsilon": (T_F32, rms_eps),
         f"{a}.rope.freq_base": (T_F32, rope_freq_base),
-        f"{a}.rope.dimension_count": (T_U32, n_embd // n_head),
+        f"{a}.rope.dimension_count": (T_U32, rope_dimension_count or n_embd // n_head),
         f"{a}.vocab_size": (T_U32, n_vocab),
         "tokenizer.ggml.model": (T_STR, "no_vocab"),
     }
+    kv.update(extra)
+    return kv
 
 
 # engine tensor kind (include/prima_mi355.h enum pm355_tensor_kind) -> GGUF base name (LLM_TENSOR_NAMES src/llama.cpp:560-600)

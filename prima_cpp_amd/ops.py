@@ -415,16 +415,29 @@ def rope_table(pos, head_dim, freq_factors=None, mode=0, n_ctx_orig=8192, freq_b
     return tab
 
 
+def mul_mat_vec_qkv_check(ws, n_head_kv, head_dim, n_rot=None, neox=False):
+    """pm355_mul_mat_vec_qkv_check_ex: 0 where the wq | wk | wv launch with the RoPE + KV-store epilogue serves these matrices and this rotation."""
+    import ctypes as C
+    lib = L.load()
+    lib.pm355_mul_mat_vec_qkv_check_ex.restype = C.c_int
+    lib.pm355_mul_mat_vec_qkv_check_ex.argtypes = [C.c_void_p, C.c_int64] + [C.c_int] * 4
+    jobs = (MatvecJob * 3)()
+    for j, w in enumerate(ws):
+        jobs[j] = MatvecJob(w.type, 0, w.N, ptr(w.data), None, None, None, None)
+    return lib.pm355_mul_mat_vec_qkv_check_ex(C.addressof(jobs), ws[0].K, n_head_kv, head_dim, n_rot or head_dim, int(neox))
+
+
 def mul_mat_vec_qkv(ws, x, tab, pos, k_cache, v_cache, n_head_kv, head_dim, n_ctx, norm_w=None, eps=0.0, biases=None, n_rot=None,
-                    v_rowmajor=False, cell_nkv=None, neox=False):
+                    v_rowmajor=False, cell_nkv=None, neox=False, out=None):
     """wq | wk | wv mat-vecs with RoPE + F16 KV store in the epilogue: returns the rotated, F16-rounded query row [N_q] (f32);
-    the K row / V column of cache cell pos[0] (or cell_nkv[0]) are written."""
+    the K row / V column of cache cell pos[0] (or cell_nkv[0]) are written. out: optional f32 [N_q] to write the query row into
+    (tests of the refusals pre-fill it)."""
     import ctypes as C
     lib = L.load()
     lib.pm355_mul_mat_vec_qkv.restype = C.c_int
     lib.pm355_mul_mat_vec_qkv.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     jobs = (MatvecJob * 3)()
-    q = torch.empty(ws[0].N, dtype=torch.float32, device=x.device)
+    q = out if out is not None else torch.empty(ws[0].N, dtype=torch.float32, device=x.device)
     for j, w in enumerate(ws):
         jobs[j] = MatvecJob(w.type, 0, w.N, ptr(w.data), None, ptr(q) if j == 0 else None,
                             ptr(biases[j]) if biases and biases[j] is not None else None, None)
@@ -447,9 +460,10 @@ class AttnTokenArgs(__import__("ctypes").Structure):
 
 
 def attn_token(q, k, v, k_cache, v_cache, pos, cell_nkv, n_head, n_head_kv, head_dim, n_ctx, scale, flags=0, mask=None, freq_factors=None, scratch=None,
-               max_keys=0, mode=0, freq_base=10000.0, n_dims=None):
+               max_keys=0, mode=0, freq_base=10000.0, n_dims=None, n_ctx_orig=8192, freq_scale=1.0, ext_factor=0.0, attn_factor=1.0,
+               beta_fast=32.0, beta_slow=1.0):
     """pm355_attn_token: one token's RoPE + KV store + attention (the plug-in's ggml-graph mode: cell_nkv = int32 {cache cell, cells attended}); raw q / k / v
-    projections in, attention output [n_head * head_dim] out. scratch != None: the long-context (split) form."""
+    projections in, attention output [n_head * head_dim] out. scratch != None: the long-context (split) form. RoPE keywords as attn_rope_fused."""
     import ctypes as C
     lib = L.load()
     lib.pm355_attn_token.restype = C.c_int
@@ -457,7 +471,7 @@ def attn_token(q, k, v, k_cache, v_cache, pos, cell_nkv, n_head, n_head_kv, head
     out = torch.empty(n_head * head_dim, dtype=torch.float32, device=q.device)
     a = AttnTokenArgs(ptr(q), ptr(k), ptr(v), ptr(k_cache), ptr(v_cache), ptr(pos), ptr(cell_nkv), ptr(mask), ptr(freq_factors), ptr(out), ptr(scratch),
                       n_head, n_head_kv, head_dim, n_ctx, 1 if scratch is not None else 0, max_keys, float(scale), flags)
-    rp = RopeParams(n_dims or head_dim, mode, 8192, freq_base, 1.0, 0.0, 1.0, 32.0, 1.0)
+    rp = RopeParams(n_dims or head_dim, mode, n_ctx_orig, freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow)
     check(lib.pm355_attn_token(C.addressof(a), C.addressof(rp), stream_ptr()), "attn_token")
     return out
 

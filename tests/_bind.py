@@ -367,7 +367,7 @@ def rand_blocks(t, nrows, k, rng, scale=None):
 
 
 def tiny_model(rng, arch=0, n_layer=2, n_embd=256, n_head=4, n_head_kv=2, n_ff=512, n_vocab=320, n_ctx=64,
-               types=None, quantize=None, rope_freqs=False):
+               types=None, quantize=None, rope_freqs=False, rope_freq_scale=1.0):
     """Build a small Llama/Qwen2-shaped model with the Q4_K_M-style type mixture.
 
     quantize(t, w_f32[rows, k]) -> uint8 blocks; defaults to random valid blocks when None."""
@@ -400,7 +400,7 @@ def tiny_model(rng, arch=0, n_layer=2, n_embd=256, n_head=4, n_head_kv=2, n_ff=5
     d.n_ff, d.n_vocab, d.n_ctx, d.n_ctx_orig = n_ff, n_vocab, n_ctx, 8192
     d.rms_eps = 1e-5 if arch == 0 else 1e-6
     d.rope_freq_base = 500000.0 if arch == 0 else 1000000.0
-    d.rope_freq_scale = 1.0
+    d.rope_freq_scale = rope_freq_scale           # (linear RoPE scaling: 1 / the scaling factor)
     E, Eq, Ekv = n_embd, head_dim * n_head, head_dim * n_head_kv
     d.attn_norm = arr([mkf(E) for _ in range(n_layer)])
     d.wq = arr([mk("attn_q", E, Eq) for _ in range(n_layer)])
@@ -508,15 +508,17 @@ def desc_from_arrays(z):
 # the reference's own driver (oracle/_ref/llama-ref-driver-*, built by oracle/Makefile from /root/reference with the
 # committed gate patch) on GGUF files written by prima_cpp_amd/gguf.py
 # --------------------------------------------------------------------------------------------
-def write_gguf_from_arrays(path, z):
-    """A golden fixture's model arrays (desc_to_arrays) -> GGUF file the reference loader reads."""
+def write_gguf_from_arrays(path, z, rope_scaling=None, rope_dimension_count=None):
+    """A golden fixture's model arrays (desc_to_arrays) -> GGUF file the reference loader reads. rope_scaling / rope_dimension_count: the optional
+    metadata of prima_cpp_amd.gguf.model_kv ({arch}.rope.scaling.*, n_rot)."""
     import sys
     sys.path.insert(0, ROOT)
     from prima_cpp_amd import gguf as G
     hp = {f: z[f"hp_{f}"] for f in _HP_FIELDS}
     arch, L, E, H, Hkv, F, V, dh = (int(hp[k]) for k in ("arch", "n_layer", "n_embd", "n_head", "n_head_kv", "n_ff", "n_vocab", "head_dim"))
     Eq, Ekv = dh * H, dh * Hkv
-    kv = G.model_kv(arch, L, E, H, Hkv, F, V, int(hp["n_ctx_orig"]), float(hp["rms_eps"]), float(hp["rope_freq_base"]))
+    kv = G.model_kv(arch, L, E, H, Hkv, F, V, int(hp["n_ctx_orig"]), float(hp["rms_eps"]), float(hp["rope_freq_base"]),
+                    rope_scaling=rope_scaling, rope_dimension_count=rope_dimension_count)
     shapes = {"attn_norm": (E,), "wq": (E, Eq), "wk": (E, Ekv), "wv": (E, Ekv), "wo": (Eq, E), "ffn_norm": (E,),
               "ffn_gate": (E, F), "ffn_up": (E, F), "ffn_down": (F, E), "bq": (Eq,), "bk": (Ekv,), "bv": (Ekv,)}
     keys = set(z.files) if hasattr(z, "files") else set(z.keys())

@@ -16,7 +16,8 @@ def _nmse(a, b):
 
 def _hp(d):
     return dict(arch=d.arch, n_layer=d.n_layer, n_embd=d.n_embd, n_head=d.n_head, n_head_kv=d.n_head_kv,
-                head_dim=d.head_dim, n_ff=d.n_ff, n_vocab=d.n_vocab, rms_eps=d.rms_eps, rope_freq_base=d.rope_freq_base)
+                head_dim=d.head_dim, n_ff=d.n_ff, n_vocab=d.n_vocab, rms_eps=d.rms_eps, rope_freq_base=d.rope_freq_base,
+                rope_freq_scale=d.rope_freq_scale)
 
 
 @pytest.fixture(scope="module")
@@ -62,6 +63,60 @@ def test_window_prefill_and_decode_vs_oracle(E, oracle, arch):
             assert np.array_equal(w.kv(0, 1), oracle.model_kv(ho, d, 0, 1))     # V path has no transcendental: bit-exact
     oracle.model_free(ho)
     w.close()
+
+
+@pytest.mark.parametrize("arch", [0, 1])
+def test_window_prefill_and_decode_with_linear_rope_scaling(E, oracle, arch):
+    """test_window_prefill_and_decode_vs_oracle with rope_freq_scale = 0.25 (linear scaling by 4, `--rope-freq-scale`), under the same tolerances:
+    that test's 5-token prefill, a small-batch step of 5 tokens at position 5 (the mmq_i8 QKV epilogue with a 5-token cos / sin table), then
+    single-token steps (the mat-vec QKV epilogue with the per-token table). Then a prompt of 40 tokens in a fresh window (more than the small-batch
+    path takes: rope_kv_store_kernel + the F16-tile GEMMs) under the tolerance of test_prefill_mfma_path_vs_oracle, 2e-3 - that path measures
+    ~1e-3 with and without scaling. With freq_scale ignored anywhere, the K rows of that path are rotated by four times the angle."""
+    torch = E.torch
+    rng = np.random.default_rng(131 + arch)
+    d = tiny_model(rng, arch=arch, n_layer=2, n_embd=256, n_head=4, n_head_kv=2, n_ff=512, n_vocab=320, n_ctx=64,
+                   rope_freqs=(arch == 0), quantize=_quantizer(), rope_freq_scale=0.25)
+    w = E.Window(_hp(d), n_ctx=64)
+    w.load_desc(d)
+    w.finalize(max_tokens=8)
+    ho = oracle.model_new(d)
+    toks = rng.integers(0, d.n_vocab, 41).astype(np.int32)
+    steps = [(toks[:5], 0), (toks[5:10], 5), (toks[10:11], 10), (toks[11:12], 11), (toks[12:14], 12)]
+    for tk, p0 in steps:
+        hid, lg, am = w.decode(tokens=torch.from_numpy(tk).cuda(), pos0=p0, want_argmax=True)
+        h_ref, l_ref = oracle.model_eval(ho, d, tokens=tk, pos0=p0)
+        assert _nmse(hid.cpu().numpy(), h_ref) < 1e-3, p0
+        assert _nmse(lg.cpu().numpy(), l_ref) < 1e-3, p0
+        assert int(am.item()) == int(np.argmax(lg.cpu().numpy()))
+    for which in (0, 1):
+        a = w.kv(0, which).view(np.float16).astype(np.float32)
+        b = oracle.model_kv(ho, d, 0, which).view(np.float16).astype(np.float32)
+        assert _nmse(a, b) < 1e-6       # (V does not pass through the rotation: its bit-exactness is test_window_prefill_and_decode_vs_oracle's)
+    k_scaled = w.kv(0, 0).view(np.float16).astype(np.float32)[:14 * d.head_dim * d.n_head_kv]
+    w.close()
+    # the prompt path
+    w = E.Window(_hp(d), n_ctx=64)
+    w.load_desc(d)
+    w.finalize(max_tokens=40)
+    oracle.model_kv_clear(ho)
+    for tk, p0 in [(toks[:40], 0), (toks[40:41], 40)]:
+        hid, lg, _ = w.decode(tokens=torch.from_numpy(tk).cuda(), pos0=p0)
+        h_ref, l_ref = oracle.model_eval(ho, d, tokens=tk, pos0=p0)
+        assert _nmse(hid.cpu().numpy(), h_ref) < 2e-3, p0
+        assert _nmse(lg.cpu().numpy(), l_ref) < 2e-3, p0
+    a = w.kv(0, 0).view(np.float16).astype(np.float32)
+    b = oracle.model_kv(ho, d, 0, 0).view(np.float16).astype(np.float32)
+    assert _nmse(a, b) < 2e-3
+    oracle.model_free(ho)
+    w.close()
+    # the scaling is in effect: the same K rows without it are far away (a test that lost its parameter on the way would pass everything above)
+    d.rope_freq_scale = 1.0
+    h1 = oracle.model_new(d)
+    for tk, p0 in steps:
+        oracle.model_eval(h1, d, tokens=tk, pos0=p0)
+    b1 = oracle.model_kv(h1, d, 0, 0).view(np.float16).astype(np.float32)[:k_scaled.size]
+    assert _nmse(k_scaled, b1) > 1e-2
+    oracle.model_free(h1)
 
 
 def test_two_windows_hand_off_equals_single_window(E):

@@ -92,6 +92,41 @@ def test_llama_decode_plugin_vs_cpu(gpu, name, tmp_path):
     assert toks.tolist() == z["tokens"].tolist()
 
 
+ROPE_SCALINGS = {"linear": dict(type="linear", factor=4.0), "yarn": dict(type="yarn", factor=4.0, original_context_length=32768)}
+
+
+@pytest.mark.parametrize("scaling", ["linear", "yarn"])
+@pytest.mark.parametrize("name", ["llama", "qwen2"])
+def test_llama_decode_plugin_rope_scaling(gpu, name, scaling, tmp_path):
+    """A model whose file says {arch}.rope.scaling.type = linear / yarn (factor 4; Qwen2.5's documented long-context setting is the yarn one): the ROPE
+    nodes then carry freq_scale = 0.25 and, for yarn, ext_factor = 1, attn_factor = 1 + 0.1 ln 4 and the file's original context length, and the plug-in
+    passes them into the fused single-token path and the epilogue table. The tiny golden models written with those keys, plug-in against the CPU backend
+    of the same binary (the committed golden tokens were made without scaling and are not compared).
+    The yarn length is Qwen2.5's documented setting (factor 4, original context 32768); the helper shows pairs 12 .. 21 (llama, base 5e5) and
+    11 .. 20 (qwen2, base 1e6) of 32 on the ramp. Measured on an MI355X: logits NMSE 6e-12 / 2e-14 (llama linear / yarn) and 1e-5 / 5e-6 (qwen2, equal
+    to the reference's own avx2-vs-scalar figure on the same files).
+    A note for whoever changes the length or the prompt: the 6-token prompt runs the MFMA masked batch attention, and any implementation that is not
+    bit-identical to the CPU now and then flips an int8 re-quantization of this toy model; a flip inside the prompt's cached history shows at every
+    later step (1e-2 of max|logit|, NMSE 2e-4 - the size of the reference's own avx2-vs-scalar flips, which show at single steps). Seen with the tiny
+    llama at original context 4096 and the tiny qwen2 at 3000; the same files agree with the CPU to 1e-7 when the prompt is fed token by token, when
+    the graphs run node by node, or with the prompt's tokens + 7."""
+    from _rope_cases import assert_three_yarn_regimes
+    z = np.load(os.path.join(HERE, "golden", f"tiny_{name}_decode.npz"))
+    rs = ROPE_SCALINGS[scaling]
+    if scaling == "yarn":
+        assert_three_yarn_regimes(int(z["hp_head_dim"]), float(z["hp_rope_freq_base"]), rs["original_context_length"])
+    path = write_gguf_from_arrays(str(tmp_path / f"tiny_{name}_{scaling}.gguf"), z, rope_scaling=rs)
+    n = len(z["tokens"])
+    toks, logits, stats = run_llama_driver(path, z["prompt"], n, ngl=99, n_ctx=int(z["hp_n_ctx"]), extra_args=GPU_ARGS)
+    assert "MI355X0" in stats["stderr"], "no layer was placed in the MI355 buffer type"
+    assert f"freq_scale_train = {1.0 / rs['factor']:g}" in stats["stderr"] and f"rope scaling     = {scaling}" in stats["stderr"], stats["stderr"][-3000:]
+    ts, ls = _check(f"tiny_{name} rope scaling {scaling}", toks, logits, path, z["prompt"], n, int(z["hp_n_ctx"]))
+    # the scaling is in effect: the same tokens through the file without the keys give other logits
+    plain = write_gguf_from_arrays(str(tmp_path / f"tiny_{name}.gguf"), z)
+    _, l0, _ = run_llama_driver(plain, z["prompt"], n, ngl=0, n_ctx=int(z["hp_n_ctx"]), force=toks[:-1], flavour="scalar")
+    assert _nmse(ls, l0) > 1e-3, _nmse(ls, l0)
+
+
 @pytest.mark.parametrize("name", ["llama", "qwen2"])
 def test_llama_decode_plugin_flash_attn(gpu, name, tmp_path):
     """--flash-attn graphs (GGML_OP_FLASH_ATTN_EXT, non-transposed F16 V cache, F16 mask; llm_build_kqv src/llama.cpp:10075-10095)

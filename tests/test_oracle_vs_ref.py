@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from _bind import F16, Q4_K, Q5_K, Q6_K, Q8_0, QUANT_TYPES, TYPE_NAMES, rand_blocks, row_size, tiny_model, vec_dot_type
+from _rope_cases import POSITIONS, ROWS, ROW_IDS, freq_factors, rope_kw
 
 
 def _acts(rng, k, kind):
@@ -157,6 +158,24 @@ def test_rope_bitexact(oracle, ref_scalar, mode, with_ff, yarn):
     if yarn:
         kw.update(freq_scale=0.25, ext_factor=1.0, attn_factor=1.1, n_ctx_orig=4096)
     assert np.array_equal(oracle.rope(x, pos, **kw).view(np.uint32), ref_scalar.rope(x, pos, **kw).view(np.uint32))
+    # far positions (a one-ulp deviation in theta is amplified by the position) and partial rotation, where tests/test_gpu_rope.py leans on the oracle
+    far = np.array([32765, 65536, 131071, 4095, 37], dtype=np.int32)
+    for n_dims in (64, 96, 128):
+        kw["n_dims"] = n_dims
+        assert np.array_equal(oracle.rope(x, far, **kw).view(np.uint32), ref_scalar.rope(x, far, **kw).view(np.uint32)), n_dims
+
+
+@pytest.mark.parametrize("row", ROWS, ids=ROW_IDS)
+def test_rope_bitexact_on_the_gpu_tests_rows(oracle, ref_scalar, row):
+    """The parameter rows of tests/test_gpu_rope.py (beta_fast / beta_slow, attn_factor, n_ctx_orig, freq factors, n_dims as there) at its positions:
+    the oracle those tests compare every kernel with is the reference bit for bit."""
+    rng = np.random.default_rng(12)
+    pos = np.concatenate([np.arange(p, p + 4) for p in POSITIONS] + [[65536]]).astype(np.int32)
+    x = rng.normal(0, 1, (pos.size, 3, row.dh)).astype(np.float32)
+    kw = dict(rope_kw(row), freq_factors=freq_factors(row))
+    got, want = oracle.rope(x, pos, **kw), ref_scalar.rope(x, pos, **kw)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(got[:, :, row.n_dims:].view(np.uint32), x[:, :, row.n_dims:].view(np.uint32))
 
 
 def test_soft_max_bitexact(oracle, ref_scalar):
