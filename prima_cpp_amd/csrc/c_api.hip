@@ -158,6 +158,14 @@ static int gemv_rc(int rc) {
         default: return fail(PM355_E_HIP, "mul_mat_vec_q: launch", hipGetLastError());
     }
 }
+// pm_launch_gemm's return codes (pm355_kernels.h); what = the entry's name
+static int gemm_rc(int rc, const char * what) {
+    if (rc == 0) return 0;
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", what, rc == -1 ? "weight type" : rc == -2 ? "K % 256 (K % 64 for Q8_0) and N % 4 required"
+                                             : rc == -5 ? "type / shape not served by the prompt kernel" : "scratch allocation");
+    return fail(rc == -1 || rc == -5 ? PM355_E_UNSUPPORTED : rc == -2 ? PM355_E_SHAPE : PM355_E_HIP, msg);
+}
 int pm355_mul_mat_vec_q(int type, const void * W, const void * W2, int64_t K, int64_t N, const void * xq, int ncols,
                         float * y, int64_t y_stride, const float * bias, const float * resid, pm355_stream_t st) {
     if (ncols < 1 || ncols > 8) return fail(PM355_E_RANGE, "mul_mat_vec_q: ncols must be 1..8");
@@ -242,31 +250,29 @@ int pm355_mul_mat_vec_fused_check(const pm355_matvec_job * jobs, int njobs, int6
 int pm355_mul_mat_q_mfma(int type, const void * W, int64_t K, int64_t N, const float * x, int64_t n_tokens, float * y,
                          const float * bias, const float * resid, pm355_stream_t st) {
     (void) hipGetLastError();
-    const int rc = pm_launch_gemm_q(type, W, x, y, (int) K, (int) N, (int) n_tokens, bias, resid, S(st));
-    if (rc == -1) return fail(PM355_E_UNSUPPORTED, "mul_mat_q_mfma: weight type");
-    if (rc == -2) return fail(PM355_E_SHAPE, "mul_mat_q_mfma: K % 256 (K % 64 for Q8_0) and N % 4 required");
+    const pm_gemm_job jb = {type, (int) N, W, y, nullptr, bias, resid, nullptr, 0};
+    const int rc = gemm_rc(pm_launch_gemm(&jb, 1, {x, nullptr}, (int) K, (int) n_tokens, 0, S(st)), "mul_mat_q_mfma");
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
 int pm355_mul_mat_q_mfma_multi(const pm355_gemm_job * jobs, int njobs, int64_t K, const float * x, int64_t n_tokens, pm355_stream_t st) {
     (void) hipGetLastError();
     if (!jobs || njobs < 1 || njobs > 4 || !x) return fail(PM355_E_RANGE, "mul_mat_q_mfma_multi: 1..4 jobs");
-    pm_gemm_pf_job jb[4];
+    pm_gemm_job jb[4];
     for (int j = 0; j < njobs; ++j) jb[j] = {jobs[j].type, (int) jobs[j].N, jobs[j].W, jobs[j].y, nullptr, jobs[j].bias, jobs[j].resid, nullptr, 0};
-    const int rc = pm_launch_gemm_q_multi(jb, njobs, x, nullptr, (int) K, (int) n_tokens, S(st));
-    if (rc == -1) return fail(PM355_E_UNSUPPORTED, "mul_mat_q_mfma_multi: weight type");
-    if (rc == -2) return fail(PM355_E_SHAPE, "mul_mat_q_mfma_multi: K % 256 (K % 64 for Q8_0) and N % 4 required");
-    if (rc) return fail(PM355_E_HIP, "mul_mat_q_mfma_multi: scratch allocation");
+    const int rc = gemm_rc(pm_launch_gemm(jb, njobs, {x, nullptr}, (int) K, (int) n_tokens, 0, S(st)), "mul_mat_q_mfma_multi");
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
 int pm355_mul_mat_q_mfma_pair(int type, const void * W_gate, const void * W_up, int64_t K, int64_t N, const float * x, int64_t n_tokens, float * y, pm355_stream_t st) {
     (void) hipGetLastError();
     if (!W_gate || !W_up || !x || !y) return fail(PM355_E_SHAPE, "mul_mat_q_mfma_pair: null pointer");
-    if (pm_gemm_pf_check(type, (int) K, (int) N, (int) n_tokens)) return fail(PM355_E_UNSUPPORTED, "mul_mat_q_mfma_pair: type / shape not served by the prompt kernel");
-    const pm_gemm_pf_job jb[2] = {{type, (int) N, W_gate, nullptr, nullptr, nullptr, nullptr, nullptr, 0}, {type, (int) N, W_up, y, nullptr, nullptr, nullptr, nullptr, 0}};
-    const int rc = pm_launch_gemm_q_pair(jb, x, (int) K, (int) n_tokens, S(st));
-    if (rc) return fail(PM355_E_HIP, "mul_mat_q_mfma_pair: launch");
+    // (no f32 gate buffer: one launch of pair tiles, or refused)
+    const pm_gemm_job jb[2] = {{type, (int) N, W_gate, nullptr, nullptr, nullptr, nullptr, nullptr, 0}, {type, (int) N, W_up, y, nullptr, nullptr, nullptr, nullptr, 0}};
+    const int rc = gemm_rc(pm_launch_gemm(jb, 2, {x, nullptr}, (int) K, (int) n_tokens, 1, S(st)), "mul_mat_q_mfma_pair");
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -610,6 +610,14 @@ LayerPath layer_path(const pm355_model * m, const Layer & L, int T) {
     if (big_ok) return LayerPath::prompt_i8;
     return T > (small_ok ? MMQ_MAX_TOKENS : VEC_MAX_TOKENS) ? LayerPath::prompt_f16 : LayerPath::small;
 }
+// the F16 prompt GEMM (pm_launch_gemm, mmq.hip) over tensors of the model
+pm_gemm_job gemm_job(const Tensor & w, float * y, void * yh, const float * bias, const float * resid) {
+    return {w.type, (int) w.N, w.d, y, yh, bias, resid, nullptr, 0};
+}
+int gemm1(const Tensor & w, pm_gemm_acts x, float * y, void * yh, const float * bias, const float * resid, int T, hipStream_t st) {
+    const pm_gemm_job j = gemm_job(w, y, yh, bias, resid);
+    return pm_launch_gemm(&j, 1, x, (int) w.K, T, 0, st);
+}
 // prompts on the integer matrix cores over Q8_K activations (PM355_PROMPT_I8=1, mmq_big.hip)
 int layer_prompt_i8(pm355_model * m, const Layer & L, int T, const float * cur, float * x_mid, float * x_next, hipStream_t st) {
     const pm355_hparams & hp = m->hp;
@@ -631,7 +639,7 @@ int layer_prompt_i8(pm355_model * m, const Layer & L, int T, const float * cur, 
     (void) hipStreamWaitEvent(m->side, m->side_a, 0);
     rc |= GI(L.t[PM355_T_WK], m->k, (const float *) L.t[PM355_T_BK].d, nullptr);
     rc |= wv8 ? GI(wv, m->v, (const float *) L.t[PM355_T_BV].d, nullptr, m->side)
-              : pm_launch_gemm_q_h(wv.type, wv.d, nullptr, m->xn, m->v, nullptr, (int) wv.K, (int) wv.N, T, (const float *) L.t[PM355_T_BV].d, nullptr, nullptr, 0, m->side);
+              : gemm1(wv, {nullptr, m->xn}, m->v, nullptr, (const float *) L.t[PM355_T_BV].d, nullptr, T, m->side);
     (void) hipEventRecord(m->side_b, m->side);
     (void) hipStreamWaitEvent(st, m->side_b, 0);
     if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: qkv mat-mul (integer matrix cores)");
@@ -656,51 +664,30 @@ int layer_prompt_f16(pm355_model * m, const Layer & L, int T, const float * cur,
     const pm355_hparams & hp = m->hp;
     const int E = hp.n_embd, H = hp.n_head, Hkv = hp.n_head_kv, dh = hp.head_dim;
     const float kq_scale = 1.0f / sqrtf((float) dh);
-    auto G = [&](const Tensor & w, const void * xh, float * y, void * yh, const float * bias, const float * resid,
-                 const float * silu_gate = nullptr, hipStream_t s2 = nullptr) {
-        return pm_launch_gemm_q_h(w.type, w.d, nullptr, xh, y, yh, (int) w.K, (int) w.N, T, bias, resid, silu_gate, 0, s2 ? s2 : st);
-    };
+    const pm_gemm_acts xn = {nullptr, m->xn};
     pm_launch_rmsnorm_q8k(cur, (const float *) L.t[PM355_T_ATTN_NORM].d, nullptr, nullptr, E, T, hp.rms_eps, st, m->xn);
     // wq | wk | wv: ONE launch over the shared activations, each matrix with its own quant type (mmq_pf.hip jobs; wk / wv alone - N = n_head_kv * head_dim -
     // filled a fraction of the chip: 212 TFLOP/s as their own launches)
-    int rc;
-    {
-        const Tensor & wq = L.t[PM355_T_WQ], & wk = L.t[PM355_T_WK], & wv = L.t[PM355_T_WV];
-        const pm_gemm_pf_job qkvj[3] = {
-            {wq.type, (int) wq.N, wq.d, m->q, nullptr, (const float *) L.t[PM355_T_BQ].d, nullptr, nullptr, 0},
-            {wk.type, (int) wk.N, wk.d, m->k, nullptr, (const float *) L.t[PM355_T_BK].d, nullptr, nullptr, 0},
-            {wv.type, (int) wv.N, wv.d, m->v, nullptr, (const float *) L.t[PM355_T_BV].d, nullptr, nullptr, 0}};
-        rc = pm_launch_gemm_q_multi(qkvj, 3, nullptr, m->xn, E, T, st);
-    }
-    if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: qkv gemm");
+    const pm_gemm_job qkv[3] = {gemm_job(L.t[PM355_T_WQ], m->q, nullptr, (const float *) L.t[PM355_T_BQ].d, nullptr),
+                                gemm_job(L.t[PM355_T_WK], m->k, nullptr, (const float *) L.t[PM355_T_BK].d, nullptr),
+                                gemm_job(L.t[PM355_T_WV], m->v, nullptr, (const float *) L.t[PM355_T_BV].d, nullptr)};
+    if (pm_launch_gemm(qkv, 3, xn, E, T, 0, st)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: qkv gemm");
     const long kvs = (long) hp.n_ctx * Hkv * dh;
     pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kvs,
                             (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st);
-    bool att_h = true;
+    pm_gemm_acts att = {nullptr, m->att};                        // the prefill attention kernel writes F16, the decode kernel f32
     if (pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, nullptr, T, H, Hkv, dh, hp.n_ctx, kq_scale, st, nullptr, 0, 0, 0, 0, m->att)) {
-        att_h = false;
+        att = {m->att, nullptr};
         if (pm_launch_attn_decode(attn_args(m, L, T, kvs), st)) return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
     }
-    const Tensor & wo = L.t[PM355_T_WO];
-    if (att_h ? G(wo, m->att, x_mid, nullptr, nullptr, cur)
-              : pm_launch_gemm_q_ex(wo.type, wo.d, m->att, x_mid, (int) wo.K, (int) wo.N, T, nullptr, cur, nullptr, 0, st))
-        return seterr(m, PM355_E_UNSUPPORTED, "prefill: wo gemm");
+    if (gemm1(L.t[PM355_T_WO], att, x_mid, nullptr, nullptr, cur, T, st)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: wo gemm");
     pm_launch_rmsnorm_q8k(x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, nullptr, nullptr, E, T, hp.rms_eps, st, m->xn);
-    {
-        // ffn_gate | ffn_up as ONE launch of pair tiles: h2 = F16(silu(gate) * up) comes out of the up waves' epilogue, the gate result crosses over inside
-        // the workgroup and never reaches HBM (two launches: gate as f32, read back by ffn_up's epilogue - 2 x T x n_ff x 4 bytes per layer)
-        const Tensor & wg = L.t[PM355_T_FFN_GATE], & wu = L.t[PM355_T_FFN_UP];
-        const pm_gemm_pf_job gu[2] = {{wg.type, (int) wg.N, wg.d, nullptr, nullptr, nullptr, nullptr, nullptr, 0},
-                                      {wu.type, (int) wu.N, wu.d, nullptr, m->h2, nullptr, nullptr, nullptr, 0}};
-        if (wg.type == wu.type && wg.N == wu.N && pm_gemm_pf_check(wg.type, E, (int) wg.N, T) == 0 && pm_gemm_pf_enabled())
-            rc = pm_launch_gemm_pf_ex(gu, 2, m->xn, E, T, 1, st);
-        else {
-            rc = G(wg, m->xn, m->h, nullptr, nullptr, nullptr);
-            rc |= G(wu, m->xn, nullptr, m->h2, nullptr, nullptr, m->h);                          // h2 = F16(silu(gate) * up), in the epilogue
-        }
-    }
-    if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: gate/up gemm");
-    return G(L.t[PM355_T_FFN_DOWN], m->h2, x_next, nullptr, nullptr, x_mid) ? seterr(m, PM355_E_UNSUPPORTED, "prefill: down gemm") : 0;
+    // ffn_gate | ffn_up as ONE launch of pair tiles: h2 = F16(silu(gate) * up) comes out of the up waves' epilogue, the gate result crosses over inside
+    // the workgroup and never reaches HBM. Where the pair launch does not serve the layer: two launches, gate as f32 into h, read back by ffn_up's
+    // epilogue (2 x T x n_ff x 4 bytes per layer)
+    const pm_gemm_job gu[2] = {gemm_job(L.t[PM355_T_FFN_GATE], m->h, nullptr, nullptr, nullptr), gemm_job(L.t[PM355_T_FFN_UP], nullptr, m->h2, nullptr, nullptr)};
+    if (pm_launch_gemm(gu, 2, xn, E, T, 1, st)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: gate/up gemm");
+    return gemm1(L.t[PM355_T_FFN_DOWN], {nullptr, m->h2}, x_next, nullptr, nullptr, x_mid, T, st) ? seterr(m, PM355_E_UNSUPPORTED, "prefill: down gemm") : 0;
 }
 // small batches (2..32 tokens) with NORM rope: RoPE + KV store ride in the epilogue of the wq | wk | wv small-batch launch; run_window writes
 // the tokens' cos / sin tables once for all layers. PM355_SMALL_ROPE_EPI=0: the separate rope_kv_store launch

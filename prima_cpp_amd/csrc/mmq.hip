@@ -17,7 +17,7 @@
 #include "pm355_kernels.h"
 #include <stdlib.h>
 
-// what pm_launch_gemm_q_h serves (through mmq_pf.hip where that takes the shape, else with the kernels of this file): every quantized weight type
+// what pm_launch_gemm serves (through mmq_pf.hip where that takes the shape, else with the kernels of this file): every quantized weight type
 constexpr uint32_t GEMM_Q_TYPES = PM_QUANT_WEIGHTS;
 
 namespace {
@@ -583,52 +583,33 @@ __global__ __launch_bounds__(512) void gemm_q_f16_kernel2(GemmP p) {
 
 } // namespace
 
-// f16 copy of the activations: one scratch buffer per DEVICE (a process may drive several GPUs through the plug-in), grown
-// on demand; GEMM calls of one device are issued from one host thread (ggml-backend stream semantics)
-static _Float16 * g_xh[16] = {};
-static size_t g_xh_elems[16] = {};
-
-int pm_launch_gemm_q(int type, const void * W, const float * X, float * Y, int K, int N, int T, const float * bias,
-                     const float * resid, hipStream_t st) {
-    return pm_launch_gemm_q_ex(type, W, X, Y, K, N, T, bias, resid, nullptr, 0, st);
-}
-
-// silu_gate: Y = silu(gate[t][n]) * (W.x + bias) (gate may alias Y). reuse_x != 0: the per-device f16 scratch already holds
-// the f16 copy of THIS X (previous call on this stream with the same X, T, K): skip the conversion.
-int pm_launch_gemm_q_ex(int type, const void * W, const float * X, float * Y, int K, int N, int T, const float * bias,
-                        const float * resid, const float * silu_gate, int reuse_x, hipStream_t st) {
-    return pm_launch_gemm_q_h(type, W, X, nullptr, Y, nullptr, K, N, T, bias, resid, silu_gate, reuse_x, st);
-}
-
-// F16 plumbing between the prefill kernels: x_f16 != null = the activations are already F16 [T][K] (written by the producing kernel:
-// rms-norm, attention, the previous GEMM's epilogue) - no conversion pass, no scratch; y_f16 != null = the result is stored as F16 [T][N]
-// (the rounding the next GEMM's conversion pass would apply) and Y is not written.
-int pm_launch_gemm_q_h(int type, const void * W, const float * X, const void * x_f16, float * Y, void * y_f16, int K, int N, int T,
-                       const float * bias, const float * resid, const float * silu_gate, int reuse_x, hipStream_t st) {
-    if (K % 64 || (!pm_q80_family(type) && K % 256) || N % 4) return -2;
-    if (!pm_in_set(GEMM_Q_TYPES, type)) return -1;
+// The F16 copy of f32 activations X [need = T * K values, a multiple of 8]: one scratch buffer per DEVICE (a process may drive several GPUs through the
+// plug-in), grown on demand; GEMM calls of one device are issued from one host thread (ggml-backend stream semantics). Returns the scratch, or null (device /
+// allocation). Growing synchronizes the device and allocates inside a launch path: the advisor's finding on pf_workspace holds here as well, and
+// this function is the one place its fix has to reach.
+static const _Float16 * gemm_x_f16(const float * X, size_t need, hipStream_t st) {
+    static _Float16 * g_xh[16] = {};
+    static size_t g_xh_elems[16] = {};
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-    const size_t need = (size_t) T * K;
-    if (!x_f16 && need > g_xh_elems[dev]) {
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+    if (need > g_xh_elems[dev]) {
         if (g_xh[dev]) { (void) hipDeviceSynchronize(); (void) hipFree(g_xh[dev]); }
-        if (hipMalloc((void **) &g_xh[dev], need * 2) != hipSuccess) { g_xh[dev] = nullptr; g_xh_elems[dev] = 0; return -3; }
+        if (hipMalloc((void **) &g_xh[dev], need * 2) != hipSuccess) { g_xh[dev] = nullptr; g_xh_elems[dev] = 0; return nullptr; }
         g_xh_elems[dev] = need;
     }
-    _Float16 * xh = x_f16 ? (_Float16 *) x_f16 : g_xh[dev];
-    if (!reuse_x && !x_f16) hipLaunchKernelGGL(cvt_f16_kernel, dim3((unsigned) ((need / 8 + 255) / 256)), dim3(256), 0, st, X, xh, (long) (need / 8));
+    hipLaunchKernelGGL(cvt_f16_kernel, dim3((unsigned) ((need / 8 + 255) / 256)), dim3(256), 0, st, X, g_xh[dev], (long) (need / 8));
+    return g_xh[dev];
+}
+
+// One job on the kernels of this file (first / second generation); force = PM355_GEMM_KERNEL
+static void gemm_q_launch(const pm_gemm_job & b, const _Float16 * xh, int K, int T, int force, hipStream_t st) {
+    const int type = b.type, N = b.N;
     static const int exp_sw = [] { const char * e = getenv("PM355_GEMM_EXP"); return e ? atoi(e) : 0; }();
-    static const int force = [] { const char * e = getenv("PM355_GEMM_KERNEL"); return e ? atoi(e) : 0; }();
-    // third generation (mmq_pf.hip: LDS-DMA for every byte, weights dequantized in registers) wherever it serves the shape; PM355_GEMM_KERNEL=1 / 2 keep the older kernels (A/B)
-    if ((force == 0 || force == 3) && pm_gemm_pf_check(type, K, N, T) == 0) {
-        const pm_gemm_pf_job job = {type, N, W, Y, y_f16, bias, resid, silu_gate, (long) N};
-        return pm_launch_gemm_pf(&job, 1, xh, K, T, st);
-    }
-    const long rs = (long) pm_weight_row_stride(type, K);
-    // a launch over weight rows [r0, r0 + n): every per-column pointer is advanced, the token stride stays N
+    const long rs = (long) pm_weight_row_stride(type, K), ldy = b.ldy ? b.ldy : (long) N;
+    // a launch over weight rows [r0, r0 + n): every per-column pointer is advanced, the token stride stays ldy
     auto params = [&](int r0, int n) {
-        GemmP p = {(const uint8_t *) W + (long) r0 * rs, xh, Y ? Y + r0 : nullptr, bias ? bias + r0 : nullptr, resid ? resid + r0 : nullptr,
-                   silu_gate ? silu_gate + r0 : nullptr, rs, K, n, T, (long) N, y_f16 ? (_Float16 *) y_f16 + r0 : nullptr, exp_sw};
+        GemmP p = {(const uint8_t *) b.W + (long) r0 * rs, xh, b.Y ? b.Y + r0 : nullptr, b.bias ? b.bias + r0 : nullptr, b.resid ? b.resid + r0 : nullptr,
+                   b.silu_gate ? b.silu_gate + r0 : nullptr, rs, K, n, T, ldy, b.Yh ? (_Float16 *) b.Yh + r0 : nullptr, exp_sw};
         return p;
     };
     auto launch2 = [&](int r0, int n) {               // 256 x 256 tiles
@@ -669,7 +650,7 @@ int pm_launch_gemm_q_h(int type, const void * W, const float * X, const void * x
     const int tn = (N + BM2 - 1) / BM2, tt = (T + BN2 - 1) / BN2;
     const long wg2 = (long) tn * tt;
     const bool use2 = force == 2 || (force != 1 && 2 * wg2 >= cus);     // at least half the CUs get a 256 x 256 tile
-    if (!use2) { launch1(0, N); return 0; }
+    if (!use2) { launch1(0, N); return; }
     // Tail: one 256 x 256 workgroup occupies a CU, so tn * tt tiles take ceil(tiles / CUs) rounds and the last one may be mostly empty
     // (ffn_gate of the 70B shape at 2048 tokens: 896 tiles = 3.5 rounds, 12.5 % of the launch idle). The weight rows of the last partial
     // round go to the 128 x 256 kernel instead (twice the workgroups, ~0.62 of a big tile's time each): [0, N1) = whole rounds of big
@@ -682,60 +663,57 @@ int pm_launch_gemm_q_h(int type, const void * W, const float * X, const void * x
             const long small = (long) ((N - N1 + BM - 1) / BM) * ((T + BN - 1) / BN);
             const double t_old = (double) (full + 1);
             const double t_new = (double) ((long) tn_full * tt + cus - 1) / cus + 0.62 * (double) ((small + cus - 1) / cus);
-            if (t_new < t_old - 0.05) { launch2(0, N1); launch1(N1, N - N1); return 0; }
+            if (t_new < t_old - 0.05) { launch2(0, N1); launch1(N1, N - N1); return; }
         }
     }
     launch2(0, N);
-    return 0;
 }
 
-// Several matrices over the same activations: f32 X is converted to F16 once (x_f16 != null: already F16, e.g. written by the producing kernel);
-// one launch of the third-generation kernel when it serves every job, else one launch per job.
-int pm_launch_gemm_q_multi(const pm_gemm_pf_job * jobs, int njobs, const float * X, const void * x_f16, int K, int T, hipStream_t st) {
-    if (njobs < 1 || njobs > 4 || !jobs || (!X && !x_f16)) return -2;
+// The prompt GEMM's one entry: njobs <= 4 matrices over the same activations x [T][K] (struct pm_gemm_job / pm_gemm_acts, pm355_kernels.h).
+// "pf" = the third-generation kernel (mmq_pf.hip: LDS-DMA for every byte, weights dequantized in registers).
+//  - Validation, per job: K % 64, K % 256 outside the Q8_0 family, N % 4 (-2); the type in GEMM_Q_TYPES (-1). The first failing job's code is returned
+//    and nothing is launched.
+//  - Activations: x.f32 is converted into the per-device F16 scratch ONCE per call and every job of the call reads the scratch (-3: device / scratch);
+//    x.f16 (written by the producing kernel: rms-norm, attention, the previous GEMM's epilogue) is read in place - no conversion, no scratch.
+//  - pf in ONE launch: when the switch allows it, pm_gemm_pf_check serves every job, and the jobs have at most two distinct types, none of a two-type
+//    set of the Q8_0 family (Q8_0 / Q5_0 go as launches of their own).
+//  - Otherwise one launch per job: pf where pm_gemm_pf_check serves the job, else the 256 x 256 / 128 x 256 kernels of this file (gemm_q_launch).
+//  - pair != 0: jobs = {ffn_gate, ffn_up}, jobs[1]'s output = silu(W0 . x) * (W1 . x). The pf pair launch where it serves the shape (same type, same N:
+//    the gate result never leaves the chip, jobs[0]'s outputs are not written); else, when jobs[0].Y names an f32 gate buffer, gate goes there and up
+//    follows as a launch of its own with silu_gate = jobs[0].Y; else -5.
+//  - PM355_GEMM_KERNEL = 1 / 2 (read here and nowhere else) switches pf off for every call that has a fallback (A/B against the older kernels). A pair
+//    call without a gate buffer has none and ignores the switch.
+int pm_launch_gemm(const pm_gemm_job * jobs, int njobs, pm_gemm_acts x, int K, int T, int pair, hipStream_t st) {
+    if (!jobs || njobs < 1 || njobs > 4 || (pair && njobs != 2) || !x.f32 == !x.f16) return -2;
     static const int force = [] { const char * e = getenv("PM355_GEMM_KERNEL"); return e ? atoi(e) : 0; }();
-    bool all_pf = force == 0 || force == 3;
+    const bool pf_on = force == 0 || force == 3;
+    bool pf[4], one = pf_on;
     int nty = 0, ty[4];
     for (int j = 0; j < njobs; ++j) {
-        all_pf = all_pf && pm_gemm_pf_check(jobs[j].type, K, jobs[j].N, T) == 0;
+        const int type = jobs[j].type, N = jobs[j].N;
+        if (K % 64 || (!pm_q80_family(type) && K % 256) || N % 4) return -2;
+        if (!pm_in_set(GEMM_Q_TYPES, type)) return -1;
+        pf[j] = pm_gemm_pf_check(type, K, N, T) == 0;
+        one = one && pf[j];
         bool seen = false;
-        for (int q = 0; q < nty; ++q) seen = seen || ty[q] == jobs[j].type;
-        if (!seen) ty[nty++] = jobs[j].type;
+        for (int q = 0; q < nty; ++q) seen = seen || ty[q] == type;
+        if (!seen) ty[nty++] = type;
     }
-    all_pf = all_pf && nty <= 2;
-    if (nty == 2 && (pm_q80_family(ty[0]) || pm_q80_family(ty[1]))) all_pf = false;      // (Q8_0 / Q5_0 go as launches of their own)
-    int rc = 0;
+    one = one && nty <= 2 && !(nty == 2 && (pm_q80_family(ty[0]) || pm_q80_family(ty[1])));
+    pm_gemm_job up = {};
+    if (pair) {
+        float * gate = jobs[0].Y;
+        one = pf[0] && nty == 1 && jobs[0].N == jobs[1].N && (pf_on || !gate);
+        if (!one && !gate) return -5;
+        up = jobs[1]; up.silu_gate = gate;
+    }
+    const _Float16 * xh = x.f16 ? (const _Float16 *) x.f16 : gemm_x_f16(x.f32, (size_t) T * K, st);
+    if (!xh) return -3;
+    if (one) return pm_launch_gemm_pf_ex(jobs, njobs, xh, K, T, pair, st);
     for (int j = 0; j < njobs; ++j) {
-        if (all_pf && j > 0) break;
-        const pm_gemm_pf_job & b = jobs[j];
-        if (all_pf) {
-            if (x_f16) return pm_launch_gemm_pf(jobs, njobs, x_f16, K, T, st);
-            // (the single-job entry converts X into the per-device scratch and launches job 0; the others follow on the same scratch)
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-            const size_t need = (size_t) T * K;
-            if (need > g_xh_elems[dev]) {
-                if (g_xh[dev]) { (void) hipDeviceSynchronize(); (void) hipFree(g_xh[dev]); }
-                if (hipMalloc((void **) &g_xh[dev], need * 2) != hipSuccess) { g_xh[dev] = nullptr; g_xh_elems[dev] = 0; return -3; }
-                g_xh_elems[dev] = need;
-            }
-            hipLaunchKernelGGL(cvt_f16_kernel, dim3((unsigned) ((need / 8 + 255) / 256)), dim3(256), 0, st, X, g_xh[dev], (long) (need / 8));
-            return pm_launch_gemm_pf(jobs, njobs, g_xh[dev], K, T, st);
-        }
-        rc |= pm_launch_gemm_q_h(b.type, b.W, X, x_f16, b.Y, b.Yh, K, b.N, T, b.bias, b.resid, b.silu_gate, j > 0 ? 1 : 0, st);
+        const pm_gemm_job & b = pair && j == 1 ? up : jobs[j];
+        if (pf_on && pf[j]) { const int rc = pm_launch_gemm_pf_ex(&b, 1, xh, K, T, 0, st); if (rc) return rc; }
+        else gemm_q_launch(b, xh, K, T, force, st);
     }
-    return rc;
-}
-
-int pm_launch_gemm_q_pair(const pm_gemm_pf_job * gate_up, const float * X, int K, int T, hipStream_t st) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-    const size_t need = (size_t) T * K;
-    if (need > g_xh_elems[dev]) {
-        if (g_xh[dev]) { (void) hipDeviceSynchronize(); (void) hipFree(g_xh[dev]); }
-        if (hipMalloc((void **) &g_xh[dev], need * 2) != hipSuccess) { g_xh[dev] = nullptr; g_xh_elems[dev] = 0; return -3; }
-        g_xh_elems[dev] = need;
-    }
-    hipLaunchKernelGGL(cvt_f16_kernel, dim3((unsigned) ((need / 8 + 255) / 256)), dim3(256), 0, st, X, g_xh[dev], (long) (need / 8));
-    return pm_launch_gemm_pf_ex(gate_up, 2, g_xh[dev], K, T, 1, st);
+    return 0;
 }

@@ -28,7 +28,7 @@
 #include <stdio.h>
 #include <mutex>
 
-// what pm_launch_gemm_pf serves. Q5_0 is left out on purpose: its form of this kernel is still to be built, and pm_launch_gemm_q_h (mmq.hip)
+// what pm_launch_gemm_pf_ex serves. Q5_0 is left out on purpose: its form of this kernel is still to be built, and pm_launch_gemm (mmq.hip)
 // takes Q5_0 matrices to the older prompt kernels
 constexpr uint32_t GEMM_PF_TYPES = pm_type_set(PM_Q4_K, PM_Q5_K, PM_Q6_K, PM_Q8_0);
 
@@ -544,12 +544,7 @@ uint8_t * pf_workspace(hipStream_t st, size_t need) {
 
 } // namespace
 
-bool pm_gemm_pf_enabled() {
-    static const int force = [] { const char * e = getenv("PM355_GEMM_KERNEL"); return e ? atoi(e) : 0; }();
-    return force == 0 || force == 3;
-}
-
-// 0 when pm_launch_gemm_pf serves (type, K, N, T)
+// 0 when pm_launch_gemm_pf_ex serves (type, K, N, T)
 int pm_gemm_pf_check(int type, int K, int N, int T) {
     if (!pm_in_set(GEMM_PF_TYPES, type)) return -1;
     if ((type == PM_Q8_0 ? K % 128 : K % 256) || K < 512 || N < 1 || N % 4 || T < 1) return -2;
@@ -595,12 +590,10 @@ void pm_gemm_pf_plan(int tiles, int K, int T, int cus, int force_nt, int force_s
 }
 
 // One launch over njobs <= 4 matrices that share the F16 activations xh [T][K]. Job j: Y_j[t][n] (f32, token stride ldy_j) or Yh_j (F16) =
-// W_j . x (+bias)(+resid)(x silu(gate)). 0, or -1 type / -2 shape
-int pm_launch_gemm_pf(const pm_gemm_pf_job * jobs, int njobs, const void * xh, int K, int T, hipStream_t st) { return pm_launch_gemm_pf_ex(jobs, njobs, xh, K, T, 0, st); }
-
+// W_j . x (+bias)(+resid)(x silu(gate)). 0, or -1 type / -2 shape / -3 split-K workspace
 // pair != 0: jobs[0] = ffn_gate, jobs[1] = ffn_up (same type, same N; jobs[0]'s outputs are ignored): jobs[1]'s output = silu(W0 . x) * (W1 . x) (+ its own bias / resid
 // before the product are NOT applied to the gate). One launch, the gate result stays on the chip.
-int pm_launch_gemm_pf_ex(const pm_gemm_pf_job * jobs, int njobs, const void * xh, int K, int T, int pair, hipStream_t st) {
+int pm_launch_gemm_pf_ex(const pm_gemm_job * jobs, int njobs, const void * xh, int K, int T, int pair, hipStream_t st) {
     if (njobs < 1 || njobs > PF_MAX_JOBS || !jobs || !xh) return -2;
     if (pair && (njobs != 2 || jobs[0].type != jobs[1].type || jobs[0].N != jobs[1].N || jobs[0].bias || jobs[0].resid || jobs[1].silu_gate)) return -2;
     PfP p = {};

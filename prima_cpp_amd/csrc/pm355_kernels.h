@@ -109,31 +109,20 @@ int pm_launch_gemv_fused(const pm_gemv_fused & a, hipStream_t st);
 int pm_gemv_fused_check(const pm_gemv_fused & a);      // the validation part of pm_launch_gemv_fused only
 int pm_gemv_fused_grid(const pm_gemv_fused & a);       // workgroups pm_launch_gemv_fused would launch (= partials written through ss_out), or < 0
 
-// batched (prefill) GEMM on MFMA: Y[T][N] = X[T][K] . W[N][K]^T (+bias[n]) (+resid[t][n]); W quantized (HBM layout), X f32
-int pm_launch_gemm_q(int type, const void * W, const float * X, float * Y, int K, int N, int T, const float * bias,
-                     const float * resid, hipStream_t st);
+// batched (prefill) GEMM on MFMA: up to 4 matrices W_j [N_j][K] (quantized, HBM layout) over the same activations x [T][K]. Job: Y[t * ldy + n] (f32) or, when
+// Yh != null, Yh[t * ldy + n] (F16; Y is not written) = W . x (+ bias[n]) (+ resid[t * ldy + n]) (* silu(silu_gate[t * ldy + n])); ldy == 0 means N.
+// pair != 0: jobs = {ffn_gate, ffn_up}, jobs[1]'s output = silu(W0 . x) * (W1 . x). The routing between the kernel generations is written at pm_launch_gemm
+// (mmq.hip). 0, or -1 type / -2 shape / -3 device or scratch / -5 a pair launch that is not served and has no f32 gate buffer (jobs[0].Y) to fall back on
+struct pm_gemm_job { int type; int N; const void * W; float * Y; void * Yh; const float * bias; const float * resid; const float * silu_gate; long ldy; };
+struct pm_gemm_acts { const float * f32; const void * f16; };      // exactly one is non-null; f32 is converted once per call into a per-device F16 scratch
+int pm_launch_gemm(const pm_gemm_job * jobs, int njobs, pm_gemm_acts x, int K, int T, int pair, hipStream_t st);
 
-int pm_launch_gemm_q_ex(int type, const void * W, const float * X, float * Y, int K, int N, int T, const float * bias,
-                        const float * resid, const float * silu_gate, int reuse_x, hipStream_t st);
-int pm_launch_gemm_q_h(int type, const void * W, const float * X, const void * x_f16, float * Y, void * y_f16, int K, int N, int T,
-                       const float * bias, const float * resid, const float * silu_gate, int reuse_x, hipStream_t st);
-
-// prompt GEMM, third generation (mmq_pf.hip): up to 4 matrices (Q4_K / Q6_K, at most two types per launch) that share the F16 activations xh [T][K]
-// go out as ONE launch. Job: Y[t * ldy + n] (f32) or, when Yh != null, Yh[t * ldy + n] (F16) = W . x (+ bias[n]) (+ resid[t * ldy + n]) (* silu(silu_gate[t * ldy + n]));
-// ldy == 0 means N. pm_gemm_pf_check: 0 when (type, K, N, T) is served, -1 type, -2 shape
+// the third generation (mmq_pf.hip; Q4_K / Q5_K / Q6_K / Q8_0, at most two types per launch) behind pm_launch_gemm: pm_gemm_pf_check: 0 when (type, K, N, T)
+// is served, -1 type, -2 shape; pm_launch_gemm_pf_ex: ONE launch over jobs that all pass it, xh = the F16 activations
 struct pm_gemm_pf_plan_t { int nt, nt_t, splitk, full, grid; double cost; };
 void pm_gemm_pf_plan(int tiles, int K, int T, int cus, int force_nt, int force_s, int allow_mixed, pm_gemm_pf_plan_t * out);   // host arithmetic only (mmq_pf.hip)
-struct pm_gemm_pf_job { int type; int N; const void * W; float * Y; void * Yh; const float * bias; const float * resid; const float * silu_gate; long ldy; };
 int pm_gemm_pf_check(int type, int K, int N, int T);
-bool pm_gemm_pf_enabled();      // false under PM355_GEMM_KERNEL=1 / 2 (A/B against the older prompt kernels)
-int pm_launch_gemm_pf(const pm_gemm_pf_job * jobs, int njobs, const void * xh, int K, int T, hipStream_t st);
-// pair != 0: jobs = {ffn_gate, ffn_up} (same type and N): jobs[1]'s output = silu(W0 . x) * (W1 . x) in one launch, the gate result never leaves the chip
-int pm_launch_gemm_pf_ex(const pm_gemm_pf_job * jobs, int njobs, const void * xh, int K, int T, int pair, hipStream_t st);
-
-// up to 4 matrices over the same activations (f32 X converted once, or x_f16 given): ONE launch of mmq_pf.hip when it serves all of them, else one launch each
-int pm_launch_gemm_q_multi(const pm_gemm_pf_job * jobs, int njobs, const float * X, const void * x_f16, int K, int T, hipStream_t st);
-
-int pm_launch_gemm_q_pair(const pm_gemm_pf_job * gate_up, const float * X, int K, int T, hipStream_t st);   // f32 X -> F16 scratch -> pair launch
+int pm_launch_gemm_pf_ex(const pm_gemm_job * jobs, int njobs, const void * xh, int K, int T, int pair, hipStream_t st);
 
 int pm_device_cus();
 struct pm_rope_cfg;

@@ -248,6 +248,33 @@ def test_prefill_mfma_path_vs_oracle(E, oracle, arch):
     w.close()
 
 
+@pytest.mark.parametrize("arch,types", [(0, None), (1, None), (0, {"ffn_gate": Q4_K, "ffn_up": Q6_K})])
+def test_prompt_f16_layer_on_the_third_generation_gemm_vs_oracle(E, oracle, arch, types):
+    """A 40-token prompt (above the 32-token small-batch limit) on a model whose every K is >= 512: the layer's GEMMs are the one-launch wq | wk | wv
+    and the ffn_gate | ffn_up pair launch of mmq_pf.hip; with ffn_gate Q4_K and ffn_up Q6_K the pair falls back to two launches, ffn_up's epilogue
+    reading the f32 gate. Hidden state and logits of the prompt and of a following decode step within the reference's whole-layer backend
+    tolerance (NMSE 2e-3, the bound of test_prefill_mfma_path_vs_oracle).
+    The decode step of the mixed gate / up case is left out: the engine's 1..32-token paths refuse a layer whose ffn_gate and ffn_up differ in type
+    ("decode: ffn_gate and ffn_up of different types", run_layers_fused / small_ffn) - only the prompt path serves it, and that is what the case is for."""
+    torch = E.torch
+    rng = np.random.default_rng(91 + arch)
+    d = tiny_model(rng, arch=arch, n_layer=2, n_embd=512, n_head=4, n_head_kv=2, n_ff=1024, n_vocab=320, n_ctx=64,
+                   types=types, rope_freqs=(arch == 0), quantize=_quantizer())
+    w = E.Window(_hp(d), n_ctx=64)
+    w.load_desc(d)
+    w.finalize(max_tokens=64)
+    ho = oracle.model_new(d)
+    toks = rng.integers(0, d.n_vocab, 41).astype(np.int32)
+    for tk, p0 in ((toks[:40], 0), (toks[40:41], 40))[:2 if types is None else 1]:
+        hid, lg, _ = w.decode(tokens=torch.from_numpy(tk).cuda(), pos0=p0)
+        h_ref, l_ref = oracle.model_eval(ho, d, tokens=tk, pos0=p0)
+        nh, nl = _nmse(hid.cpu().numpy(), h_ref), _nmse(lg.cpu().numpy(), l_ref)
+        print(f"arch {arch} tokens {len(tk)}: hidden NMSE {nh:.3e} logits NMSE {nl:.3e}")
+        assert nh < 2e-3 and nl < 2e-3, (len(tk), nh, nl)
+    oracle.model_free(ho)
+    w.close()
+
+
 @pytest.mark.parametrize("flash,n_head,n_embd,n_head_kv", [("1", 8, 512, 2), ("1", 4, 512, 2), ("0", 8, 512, 2), ("1", 8, 1024, 4), ("1", 16, 1024, 8)])
 def test_long_context_split_attention_path(E, monkeypatch, flash, n_head, n_embd, n_head_kv):
     """Beyond PM355_ATTN_SPLIT_MIN positions the engine switches from the one-workgroup-per-head attention kernel to the

@@ -4,7 +4,7 @@ Integer / byte results: bit-exact. Float results: tolerance stated per test."""
 import numpy as np
 import pytest
 
-from _bind import Q4_K, Q5_K, Q6_K, Q8_0, Q8_K, QUANT_TYPES, TYPE_NAMES, rand_blocks, row_size, vec_dot_type
+from _bind import Q4_K, Q5_0, Q5_K, Q6_K, Q8_0, Q8_K, QUANT_TYPES, TYPE_NAMES, rand_blocks, row_size, vec_dot_type
 
 pytestmark = pytest.mark.gpu
 
@@ -657,6 +657,93 @@ def test_prompt_gemm_jobs_one_launch(P, oracle, types, T):
         exact = x.astype(np.float64) @ Wf.T + b.cpu().numpy()
         nm = ((y.cpu().numpy() - exact) ** 2).sum() / (exact ** 2).sum()
         assert nm < 1e-6, (t, nm)
+
+
+def _gemm_blocks(t, N, K, rng):
+    if t == Q5_0:                                          # (rand_blocks has no Q5_0: the blocks of tests/test_gpu_q5_0.py)
+        from prima_cpp_amd import gguf as G
+        return G.random_valid_blocks(Q5_0, N, K, rng, scale=1.0).reshape(-1)
+    return rand_blocks(t, N, K, rng, scale=1.0)
+
+
+def _dequant_f64(oracle, t, blocks, K, N):
+    if t == Q5_0:                                          # dequantize_row_q5_0: d * ((nibble | high bit << 4) - 16); the oracle library has no Q5_0
+        b = np.ascontiguousarray(blocks).reshape(N, K // 32, 22)
+        d = b[..., 0:2].copy().view(np.float16)[..., 0].astype(np.float64)
+        qh = b[..., 2:6].copy().view(np.uint32)[..., 0].astype(np.int64)
+        qs = b[..., 6:22].astype(np.int64)
+        j = np.arange(32)
+        nib = np.where(j < 16, qs[..., j % 16] & 0xF, qs[..., j % 16] >> 4)
+        q = (nib | (((qh[..., None] >> j) & 1) << 4)) - 16
+        return (q * d[..., None]).reshape(N, K)
+    rs = row_size(t, K)
+    return np.stack([oracle.dequantize_row(t, blocks[r * rs:(r + 1) * rs], K) for r in range(N)]).astype(np.float64)
+
+
+_JOB_LIST_CASES = [(1024, 77, (Q4_K, Q5_K, Q6_K)),         # three types
+                   (1024, 77, (Q4_K, Q4_K, Q8_0)),         # the Q8_0 family mixed in
+                   (1024, 77, (Q4_K, Q4_K, Q5_0)),         # a type the third-generation kernel does not have
+                   (256, 40, (Q4_K, Q4_K, Q6_K))]          # K < 512: the older kernels, all three reading one shared conversion
+
+
+@pytest.mark.parametrize("K,T,types", _JOB_LIST_CASES)
+def test_prompt_gemm_job_lists_served_launch_by_launch(P, oracle, K, T, types):
+    """Job lists the one-launch form does not serve go out as one launch per job over ONE F16 conversion of the activations: every job's output is
+    bit-identical to its own single launch and equals the f64 product of the dequantized weights to F16 operand rounding (NMSE < 1e-6, the bound of
+    test_prompt_gemm_jobs_one_launch)."""
+    torch = P.torch
+    rng = np.random.default_rng(85)
+    Ns = [520, 132, 256]
+    blocks = [_gemm_blocks(t, n, K, rng) for t, n in zip(types, Ns)]
+    ws = [P.upload_weight(t, b, K, n) for t, b, n in zip(types, blocks, Ns)]
+    x = rng.normal(0, 1, (T, K)).astype(np.float32)
+    biases = [torch.from_numpy(rng.normal(0, 1, n).astype(np.float32)).cuda() for n in Ns]
+    xd = _dev(P, x)
+    ys = P.mul_mat_mfma_multi(ws, xd, biases=biases)
+    for w, t, b, bl, y in zip(ws, types, biases, blocks, ys):
+        single = P.mul_mat_mfma(w, xd, bias=b)
+        assert torch.equal(y, single), t
+        exact = x.astype(np.float64) @ _dequant_f64(oracle, t, bl, K, w.N).T + b.cpu().numpy()
+        nm = ((y.cpu().numpy() - exact) ** 2).sum() / (exact ** 2).sum()
+        print(f"K {K} type {t}: NMSE {nm:.3e}")
+        assert nm < 1e-6, (t, nm)
+
+
+def test_prompt_gemm_scratch_holds_this_calls_activations(P):
+    """Two job-list calls of the same shape with different activations: the second call's outputs are those of the single launches on ITS x (the
+    per-device F16 scratch is converted anew by every call, and shared only among the jobs of one call)."""
+    torch = P.torch
+    rng = np.random.default_rng(86)
+    K, T, types = _JOB_LIST_CASES[3]
+    Ns = [520, 132, 256]
+    ws = [P.upload_weight(t, rand_blocks(t, n, K, rng, scale=1.0), K, n) for t, n in zip(types, Ns)]
+    biases = [torch.from_numpy(rng.normal(0, 1, n).astype(np.float32)).cuda() for n in Ns]
+    x1, x2 = (_dev(P, rng.normal(0, 1, (T, K)).astype(np.float32)) for _ in range(2))
+    first = P.mul_mat_mfma_multi(ws, x1, biases=biases)
+    second = P.mul_mat_mfma_multi(ws, x2, biases=biases)
+    for w, b, y1, y2 in zip(ws, biases, first, second):
+        assert torch.equal(y2, P.mul_mat_mfma(w, x2, bias=b))
+        assert not torch.equal(y2, y1)
+
+
+def test_prompt_gemm_pair_refuses_a_shape_without_pair_tiles(P):
+    """pm355_mul_mat_q_mfma_pair has no gate buffer to fall back on: K = 256 (below the third-generation kernel's 512) is refused by the argument check,
+    and y is not written."""
+    import ctypes as C
+    torch = P.torch
+    rng = np.random.default_rng(87)
+    K, N, T = 256, 256, 64
+    wg = P.upload_weight(Q4_K, rand_blocks(Q4_K, N, K, rng, scale=1.0), K, N)
+    wu = P.upload_weight(Q4_K, rand_blocks(Q4_K, N, K, rng, scale=1.0), K, N)
+    x = _dev(P, rng.normal(0, 1, (T, K)).astype(np.float32))
+    y = torch.full((T, N), -77.25, dtype=torch.float32, device="cuda")
+    lib = P.L.load()
+    lib.pm355_mul_mat_q_mfma_pair.restype = C.c_int
+    lib.pm355_mul_mat_q_mfma_pair.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    rc = lib.pm355_mul_mat_q_mfma_pair(Q4_K, P.ptr(wg.data), P.ptr(wu.data), K, N, P.ptr(x), T, P.ptr(y), P.stream_ptr())
+    assert rc != 0
+    torch.cuda.synchronize()
+    assert bool((y == -77.25).all())
 
 
 @pytest.mark.parametrize("t", [Q4_K, Q5_K, Q6_K])
