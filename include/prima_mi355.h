@@ -473,6 +473,13 @@ PM355_API int pm355_model_n_seq(const pm355_model * m);          /* KV slabs the
  * ggml-cuda/mmq.cuh:2583-2700). out5 = {tokens per tile (64 / 128 / 256), token tiles, K slices of a split tile, whole-tile slots per XCD in front of the split
  * ones (0: every tile is split, or none when slices == 1), workgroups launched}. allow_tail_split = 0: the uniform split only. */
 PM355_API int pm355_gemm_plan(int64_t n_row_tiles, int64_t K, int64_t n_tokens, int n_cus, int allow_tail_split, int32_t * out5);
+/* Launch geometry of the small-batch mat-mul (pm355_mul_mat_q_small, _multi, _mixed) for a list of 1..4 matrices (types[j], N[j] rows) x n_tokens x K on a
+ * device of n_cus CUs - the launcher's own host arithmetic, no device needed. Returns the number of passes over the weights (or a negative code when no form
+ * serves the list) and fills, for each of the first max_passes, out[8 * pass ..] = {form (0 one matrix, 1 several of one type, 2 two-part grid), first token,
+ * tokens, result registers per lane of the instantiation (4 / 8 / 16), workgroups, log2 of the row groups a workgroup works on side by side, and the same
+ * two of the last matrix's part of a two-part grid (else 0)}. with_epilogue: the wq | wk | wv launch with RoPE + KV store in its epilogue. */
+PM355_API int pm355_mul_mat_q_small_plan(const int * types, const int64_t * N, int njobs, int64_t K, int64_t n_tokens, int with_epilogue, int n_cus,
+                                         int32_t * out, int max_passes);
 /* Largest batch the library routes to the integer small-batch mat-mul (pm355_mul_mat_q_small: the CPU backend's Q8_K arithmetic, ggml/src/ggml.c:12377); larger
  * batches take the F16 prompt GEMM (pm355_mul_mat_q_mfma). 32 unless PM355_MMQ_MAX_TOKENS = 16 .. 64 says otherwise. */
 PM355_API int pm355_small_batch_max_tokens(void);

@@ -287,15 +287,26 @@ int pm355_mul_mat_q_i8(int type, const void * W, int64_t K, int64_t N, const flo
     return 0;
 }
 int pm355_mul_mat_q_i8_check(int type, int64_t K, int64_t N, int64_t n_tokens) { return pm_mmq_big_check(type, (int) K, (int) N, (int) n_tokens) ? PM355_E_UNSUPPORTED : 0; }
+// pm_launch_mmq_i8's return codes (pm355_kernels.h); what = the entry's name, unserved = what the entry says to a list no form serves (-5)
+static int mmq_rc(int rc, const char * what, const char * unserved) {
+    if (rc == 0) return 0;
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: %s", what, rc == -1 ? "weight type (Q4_K / Q5_K / Q6_K / Q8_0)"
+                                             : rc == -2 ? "1 <= n_tokens <= 64, K % 256 == 0 (Q8_0: K % 32 == 0), K >= 512 required"
+                                             : rc == -4 ? "K too large for the LDS tiles" : rc == -5 ? unserved : "scratch allocation");
+    return fail(rc == -1 || rc == -5 ? PM355_E_UNSUPPORTED : rc == -2 ? PM355_E_SHAPE : rc == -4 ? PM355_E_RANGE : PM355_E_HIP, msg);
+}
+// a job list of the C ABI's parallel arrays (types: one per job, or null and `type` for all)
+static void mmq_jobs(pm_mmq_job * jb, int njobs, const int * types, int type, const void * const * W, const int64_t * N, float * const * y, const float * const * bias) {
+    for (int j = 0; j < njobs; ++j) jb[j] = {types ? types[j] : type, (int) N[j], W[j], y[j], bias ? bias[j] : nullptr, nullptr};
+}
 int pm355_mul_mat_q_small(int type, const void * W, int64_t K, int64_t N, const void * xq, const float * x, int64_t n_tokens, float * y,
                           const float * bias, const float * resid, pm355_stream_t st) {
     (void) hipGetLastError();
     if (!xq && !x) return fail(PM355_E_RANGE, "mul_mat_q_small: neither xq nor x given");
-    const int rc = pm_launch_mmq_i8(type, W, xq, x, y, (int) K, (int) N, (int) n_tokens, bias, resid, 0, S(st));
-    if (rc == -1) return fail(PM355_E_UNSUPPORTED, "mul_mat_q_small: weight type (Q4_K / Q5_K / Q6_K / Q8_0)");
-    if (rc == -2) return fail(PM355_E_SHAPE, "mul_mat_q_small: 1 <= n_tokens <= 64, K % 256 == 0 (Q8_0: K % 32 == 0), K >= 512 required");
-    if (rc == -4) return fail(PM355_E_RANGE, "mul_mat_q_small: K too large for the LDS tiles");
-    if (rc) return fail(PM355_E_HIP, "mul_mat_q_small: scratch allocation");
+    const pm_mmq_job jb = {type, (int) N, W, y, bias, resid};
+    const int rc = mmq_rc(pm_launch_mmq_i8(&jb, 1, {xq, x, 0}, (int) K, (int) n_tokens, nullptr, S(st)), "mul_mat_q_small", "");
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -303,11 +314,11 @@ int pm355_mul_mat_q_small_multi(int type, int njobs, const void * const * W, con
                                 const void * xq, int64_t K, int64_t n_tokens, pm355_stream_t st) {
     (void) hipGetLastError();
     if (njobs < 2 || njobs > 3 || !W || !N || !y || !xq) return fail(PM355_E_RANGE, "mul_mat_q_small_multi: 2..3 jobs, pre-quantized activations");
-    int n32[3];
-    for (int j = 0; j < njobs; ++j) n32[j] = (int) N[j];
-    const int rc = pm_launch_mmq_i8_multi(type, njobs, W, n32, y, bias, xq, (int) K, (int) n_tokens, 0, S(st));
-    if (rc == -5) return fail(PM355_E_UNSUPPORTED, "mul_mat_q_small_multi: Q4_K / Q6_K, n_tokens <= 64, K % 256 == 0 required");
-    if (rc) return fail(PM355_E_HIP, "mul_mat_q_small_multi: scratch allocation");
+    pm_mmq_job jb[3];
+    mmq_jobs(jb, njobs, nullptr, type, W, N, y, bias);
+    const int rc = mmq_rc(pm_launch_mmq_i8(jb, njobs, {xq, nullptr, 0}, (int) K, (int) n_tokens, nullptr, S(st)), "mul_mat_q_small_multi",
+                          "Q4_K / Q6_K, n_tokens <= 64, K % 256 == 0 required");
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -315,15 +326,28 @@ int pm355_mul_mat_q_small_mixed(const int * types, int njobs, const void * const
                                 const void * xq, int64_t K, int64_t n_tokens, pm355_stream_t st) {
     (void) hipGetLastError();
     if (njobs < 2 || njobs > 3 || !types || !W || !N || !y || !xq) return fail(PM355_E_RANGE, "mul_mat_q_small_mixed: 2..3 jobs, pre-quantized activations");
-    int n32[3];
-    for (int j = 0; j < njobs; ++j) n32[j] = (int) N[j];
     for (int j = 1; j < njobs - 1; ++j) if (types[j] != types[0]) return fail(PM355_E_UNSUPPORTED, "mul_mat_q_small_mixed: only the LAST job may be of another type");
-    const int na = njobs - 1;
-    const int rc = pm_launch_mmq_i8_dual(types[0], na, W, n32, y, bias, types[na], W[na], n32[na], y[na], bias ? bias[na] : nullptr, xq, (int) K, (int) n_tokens, 0, S(st));
-    if (rc == -5) return fail(PM355_E_UNSUPPORTED, "mul_mat_q_small_mixed: Q4_K jobs + one Q6_K (n_tokens <= 32) / Q5_K (<= 16) job, K % 256 == 0 required");
-    if (rc) return fail(PM355_E_HIP, "mul_mat_q_small_mixed: scratch allocation");
+    pm_mmq_job jb[3];
+    mmq_jobs(jb, njobs, types, 0, W, N, y, bias);
+    // (a last job of the first job's type is pm355_mul_mat_q_small_multi's list: this entry keeps refusing it)
+    const int lrc = types[njobs - 1] == types[0] ? -5 : pm_launch_mmq_i8(jb, njobs, {xq, nullptr, 0}, (int) K, (int) n_tokens, nullptr, S(st));
+    const int rc = mmq_rc(lrc, "mul_mat_q_small_mixed", "Q4_K jobs + one Q6_K (n_tokens <= 32) / Q5_K (<= 16) job, K % 256 == 0 required");
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
+}
+int pm355_mul_mat_q_small_plan(const int * types, const int64_t * N, int njobs, int64_t K, int64_t n_tokens, int with_epilogue, int n_cus, int32_t * out, int max_passes) {
+    if (!types || !N || njobs < 1 || njobs > 4 || n_cus < 1 || !out || max_passes < 1) return fail(PM355_E_RANGE, "mul_mat_q_small_plan: 1..4 jobs, n_cus >= 1, out required");
+    pm_mmq_job jb[4];
+    for (int j = 0; j < njobs; ++j) jb[j] = {types[j], (int) N[j], nullptr, nullptr, nullptr, nullptr};
+    pm_mmq_plan_t pl;
+    if (pm_mmq_i8_plan(jb, njobs, (int) K, (int) n_tokens, with_epilogue, n_cus, &pl)) return fail(PM355_E_UNSUPPORTED, "mul_mat_q_small_plan: no form of the small-batch mat-mul serves this list");
+    for (int i = 0; i < pl.npass && i < max_passes; ++i) {
+        const pm_mmq_pass & p = pl.pass[i];
+        const int32_t v[8] = {p.form, p.t0, p.tn, p.nv, p.grid[0], p.rgb_log2[0], p.grid[1], p.rgb_log2[1]};
+        memcpy(out + 8 * i, v, sizeof(v));
+    }
+    return pl.npass;
 }
 int pm355_gemm_plan(int64_t n_row_tiles, int64_t K, int64_t n_tokens, int n_cus, int allow_tail_split, int32_t * out5) {
     if (n_row_tiles < 1 || K < 256 || n_tokens < 1 || n_cus < 8 || !out5) return fail(PM355_E_RANGE, "gemm_plan: n_row_tiles >= 1, K >= 256, n_tokens >= 1, n_cus >= 8");

@@ -273,7 +273,9 @@ void layer_release(pm355_model * m, int il, hipStream_t st) {
 }
 
 // quantize `src` [T][K] into the activation format(s) the given weights need; returns pointers
-struct ActQ { const void * k = nullptr; const void * z = nullptr; bool tab = false; };   // tab: the small-batch mat-mul's activation tables were written too
+// tab: the small-batch mat-mul's Q8_K activation tables describe this set too - the quantizer wrote them as its second output, or a served mat-mul over the set did
+// (matmul_small sets it then). The Q8_0 family's tables are re-used only straight behind pm_launch_silu_mul_q80_tab (small_ffn)
+struct ActQ { const void * k = nullptr; const void * z = nullptr; bool tab = false; };
 const int MMQ_MIN_TOKENS = 3;                           // (3 columns cost the multi-column mat-vec two passes: 57 vs 39 us on the ffn shape)
 // largest batch on the integer matrix cores (mmq_i8.hip: the CPU's Q8_K arithmetic, one weight pass per 32 tokens); beyond it the F16 GEMMs (mmq_pf.hip).
 // Round 6: 32 (was 64) - with 64-token tiles the prompt GEMM takes 33..64 tokens through a 70B layer in 304-314 us against 378-447 for two passes of the
@@ -321,16 +323,16 @@ int gemv(const Tensor & w, const Tensor * w2, const ActQ & a, int T, float * y, 
 }
 
 // 3..MMQ_MAX_TOKENS (32; on request 64) tokens: one pass over the weights per 32 tokens on the integer matrix cores (mmq_i8.hip) where the type / shape is served, else the mat-vec
-// (one to three passes per 8 columns). `prepped`: the kernel's activation tables already describe THIS activation set (set by the first
-// served call, cleared by the caller whenever the activations change)
-int matmul_small(pm355_model * m, const Tensor & w, const ActQ & a, int T, float * y, const float * bias, const float * resid, bool & prepped, hipStream_t st) {
+// (one to three passes per 8 columns). A served call leaves a.tab set: the next matrix over the same activations needs no table prologue
+pm_mmq_job mmq_job(const Tensor & w, float * y, const float * bias, const float * resid) { return {w.type, (int) w.N, w.d, y, bias, resid}; }
+int matmul_small(pm355_model * m, const Tensor & w, ActQ & a, int T, float * y, const float * bias, const float * resid, hipStream_t st) {
     // (3 / 4 tokens on the 4-slot multi-column mat-vec - two rows per activation fetch: ffn_down Q6_K 46 us - measured against this kernel once it had
     //  its operand-ordered activation table (54 us without the prologue launch): 177 vs 172 us per layer, so the matrix-core kernel keeps them)
     const bool q80 = pm_q80_family(w.type);              // Q8_0 / Q5_0 weights take Q8_0 activations; the kernel builds their tables per call
     const void * xa = q80 ? a.z : a.k;
-    if (T >= MMQ_MIN_TOKENS && T <= MMQ_MAX_TOKENS && !m->no_mmq && xa && pm_mmq_i8_check(w.type, (int) w.K, (int) w.N, T) == 0) {
-        const int rc = pm_launch_mmq_i8(w.type, w.d, xa, nullptr, y, (int) w.K, (int) w.N, T, bias, resid, q80 ? 0 : ((prepped || a.tab) ? 1 : 0), st);
-        if (rc == 0) { if (!q80) prepped = true; return 0; }
+    if (T >= MMQ_MIN_TOKENS && T <= MMQ_MAX_TOKENS && !m->no_mmq && xa) {
+        const pm_mmq_job j = mmq_job(w, y, bias, resid);
+        if (pm_launch_mmq_i8(&j, 1, {xa, nullptr, !q80 && a.tab}, (int) w.K, T, nullptr, st) == 0) { if (!q80) a.tab = true; return 0; }   // (else: type / shape not served)
     }
     return gemv(w, nullptr, a, T, y, bias, resid, st);
 }
@@ -623,7 +625,7 @@ int layer_prompt_i8(pm355_model * m, const Layer & L, int T, const float * cur, 
     const pm355_hparams & hp = m->hp;
     const int E = hp.n_embd, H = hp.n_head, Hkv = hp.n_head_kv, dh = hp.head_dim, F = hp.n_ff;
     const float kq_scale = 1.0f / sqrtf((float) dh);
-    auto TB = [&](int K) { pm_q8k_tables tb; tb.base = m->tab_big; tb.tab_bytes = (size_t) (K / 256) * (1024 + 128); tb.nsb = K / 256; return tb; };
+    auto TB = [&](int K) { return pm_q8k_tables_at(m->tab_big, K); };
     auto GI = [&](const Tensor & w, float * y, const float * bias, const float * resid, hipStream_t s2 = nullptr) {
         return pm_launch_mmq_big(w.type, w.d, m->aq_k, m->tab_big, y, (int) w.K, (int) w.N, T, bias, resid, s2 ? s2 : st);
     };
@@ -695,43 +697,24 @@ bool small_rope_epi(const pm355_model * m, int T) {
     return T >= MMQ_MULTI_MIN_TOKENS && T <= 32 && T <= MMQ_MAX_TOKENS && !m->no_mmq && !m->no_small_epi && m->qkv_epi && m->rope_tab &&
            m->rope.mode == 0 && m->hi > m->lo;
 }
-// matrices of one type that share the activations go out as ONE small-batch launch per 32 tokens: wq | wk (| wv), ffn_gate | ffn_up
-int mmq_multi(const Tensor * const * ws, float * const * ys, const float * const * bs, int n, const ActQ & a, int T, hipStream_t st,
-              const pm_qkv_epi * epi = nullptr) {
-    const void * W[3]; int N[3];
-    for (int j = 0; j < n; ++j) { W[j] = ws[j]->d; N[j] = (int) ws[j]->N; }
-    return pm_launch_mmq_i8_multi(ws[0]->type, n, W, N, ys, bs, a.k, (int) ws[0]->K, T, a.tab ? 1 : 0, st, epi);
-}
-// wq | wk | wv of a small batch (small: the small-batch mat-mul takes it). Each fused launch is tried first with RoPE + KV store in its
-// epilogue (rope_done), then without: all three of one type; else wv of another K-quant type (Q6_K / Q5_K in the Q4_K_M files) in the same
-// grid, its own workgroups (mmq_i8_dual_kernel); else wq | wk and wv alone. Otherwise one mat-mul per matrix
-int small_qkv(pm355_model * m, const Layer & L, const ActQ & a, int T, bool small, bool & rope_done, hipStream_t st) {
+// wq | wk | wv of a small batch (small: the small-batch mat-mul takes it) over one activation set: the three matrices as ONE launch (pm_launch_mmq_i8 picks the
+// form from their types), first with RoPE + KV store in its epilogue (rope_done), then without; else wq | wk as one launch and wv alone; else one mat-mul per matrix
+int small_qkv(pm355_model * m, const Layer & L, ActQ a, int T, bool small, bool & rope_done, hipStream_t st) {
     const pm355_hparams & hp = m->hp;
-    const Tensor * ws[3] = {&L.t[PM355_T_WQ], &L.t[PM355_T_WK], &L.t[PM355_T_WV]};
-    float * ys[3] = {m->q, m->k, m->v};
-    const float * bs[3] = {(const float *) L.t[PM355_T_BQ].d, (const float *) L.t[PM355_T_BK].d, (const float *) L.t[PM355_T_BV].d};
-    const Tensor & wq = *ws[0], & wk = *ws[1], & wv = *ws[2];
+    const Tensor & wq = L.t[PM355_T_WQ], & wk = L.t[PM355_T_WK], & wv = L.t[PM355_T_WV];
+    const pm_mmq_job jobs[3] = {mmq_job(wq, m->q, (const float *) L.t[PM355_T_BQ].d, nullptr), mmq_job(wk, m->k, (const float *) L.t[PM355_T_BK].d, nullptr),
+                                mmq_job(wv, m->v, (const float *) L.t[PM355_T_BV].d, nullptr)};
     const pm_qkv_epi qe = {m->rope_tab, m->d_pos, m->d_ctl, nullptr, (long) hp.n_ctx * hp.n_head_kv * hp.head_dim, L.kc, L.vc, hp.n_head_kv, hp.head_dim,
                            hp.n_ctx, m->rope.n_dims, 0, 0};
-    const pm_qkv_epi * epi = small_rope_epi(m, T) ? &qe : nullptr;
-    auto fused = [&](auto && launch) {
-        if (epi && launch(epi) == 0) return rope_done = true;
-        return launch(nullptr) == 0;
-    };
-    bool prepped = false;
-    if (small && wq.type == wk.type) {
-        if (wv.type == wq.type) {
-            if (fused([&](const pm_qkv_epi * e) { return mmq_multi(ws, ys, bs, 3, a, T, st, e); })) return 0;
-        } else {
-            const void * W[2] = {wq.d, wk.d}; const int N[2] = {(int) wq.N, (int) wk.N};
-            if (wv.K == wq.K && fused([&](const pm_qkv_epi * e) {
-                    return pm_launch_mmq_i8_dual(wq.type, 2, W, N, ys, bs, wv.type, wv.d, (int) wv.N, m->v, bs[2], a.k, (int) wq.K, T, a.tab ? 1 : 0, st, e); }))
-                return 0;
-            if (mmq_multi(ws, ys, bs, 2, a, T, st) == 0) { prepped = true; return matmul_small(m, wv, a, T, m->v, bs[2], nullptr, prepped, st); }
-        }
+    auto fused = [&](int n, const pm_qkv_epi * e) { return pm_launch_mmq_i8(jobs, n, {a.k, nullptr, a.tab}, (int) wq.K, T, e, st) == 0; };
+    if (small && wq.type == wk.type && wk.K == wq.K && wv.K == wq.K) {      // (one K per launch: a job carries none)
+        if (small_rope_epi(m, T) && fused(3, &qe)) { rope_done = true; return 0; }
+        if (fused(3, nullptr)) return 0;
+        if (fused(2, nullptr)) { a.tab = true; return matmul_small(m, wv, a, T, jobs[2].y, jobs[2].bias, nullptr, st); }
     }
+    const Tensor * ws[3] = {&wq, &wk, &wv};
     int rc = 0;
-    for (int j = 0; j < 3; ++j) rc |= matmul_small(m, *ws[j], a, T, ys[j], bs[j], nullptr, prepped, st);
+    for (int j = 0; j < 3; ++j) rc |= matmul_small(m, *ws[j], a, T, jobs[j].y, jobs[j].bias, nullptr, st);
     return rc;
 }
 // RoPE + KV store (unless the wq | wk | wv epilogue did them), attention, wo + residual -> x_mid
@@ -753,9 +736,8 @@ int small_attention(pm355_model * m, const Layer & L, int T, bool rope_done, con
         pm_launch_attn_cached(at, st) && pm_launch_attn_decode(at, st))
         return seterr(m, PM355_E_RANGE, "decode: n_ctx too large for the decode-attention kernel");
     const Tensor * wo[1] = {&L.t[PM355_T_WO]};
-    const ActQ a = quantize_for(m, m->att, H * dh, T, wo, 1, st);
-    bool prepped = false;
-    return matmul_small(m, L.t[PM355_T_WO], a, T, x_mid, nullptr, cur, prepped, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: wo gemv") : 0;
+    ActQ a = quantize_for(m, m->att, H * dh, T, wo, 1, st);
+    return matmul_small(m, L.t[PM355_T_WO], a, T, x_mid, nullptr, cur, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: wo gemv") : 0;
 }
 // ffn_norm, ffn_gate | ffn_up, silu * mul, ffn_down + residual -> x_next
 int small_ffn(pm355_model * m, const Layer & L, int T, bool small, const float * x_mid, float * x_next, hipStream_t st) {
@@ -764,16 +746,16 @@ int small_ffn(pm355_model * m, const Layer & L, int T, bool small, const float *
     const Tensor * gu[2] = {&wg, &wu};
     ActQ a = norm_quantize_for(m, x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, E, T, gu, 2, st);
     if (wg.type != wu.type) return seterr(m, PM355_E_UNSUPPORTED, "decode: ffn_gate and ffn_up of different types");
-    bool prepped = false, gu_done = false;
+    bool gu_done = false;
     // 2 tokens: the pair mat-vec with two column slots - one pass over both matrices, silu(gate) * up in its epilogue (~50 us against 60 for the
     // two-matrix launch of the matrix-core kernel + the product launch)
     const bool pair_cols = T == 2 && pm_gemv_col_slots(wg.type, true, T) == 2;
     if (!pair_cols && small && m->h2 && pm_mmq_i8_check(wg.type, (int) wg.K, (int) wg.N, T) == 0) {
         // gate and up: one weight pass each for all tokens, then silu(gate) * up (the pair mat-vec would take one launch per token)
-        float * ys[2] = {m->h, m->h2}; const float * bs[2] = {nullptr, nullptr};
-        if (mmq_multi(gu, ys, bs, 2, a, T, st) == 0) gu_done = true;
+        const pm_mmq_job jobs[2] = {mmq_job(wg, m->h, nullptr, nullptr), mmq_job(wu, m->h2, nullptr, nullptr)};
+        if (pm_launch_mmq_i8(jobs, 2, {a.k, nullptr, a.tab}, (int) wg.K, T, nullptr, st) == 0) gu_done = true;
         else if (T >= MMQ_MIN_TOKENS) {
-            if (matmul_small(m, wg, a, T, m->h, nullptr, nullptr, prepped, st) || matmul_small(m, wu, a, T, m->h2, nullptr, nullptr, prepped, st))
+            if (matmul_small(m, wg, a, T, m->h, nullptr, nullptr, st) || matmul_small(m, wu, a, T, m->h2, nullptr, nullptr, st))
                 return seterr(m, PM355_E_UNSUPPORTED, "decode: gate/up small-batch mat-mul");
             gu_done = true;
         }
@@ -790,14 +772,14 @@ int small_ffn(pm355_model * m, const Layer & L, int T, bool small, const float *
         void * tab = nullptr; size_t qb = 0, db = 0;
         if (gu_done && T >= MMQ_MIN_TOKENS && pm_mmq_i8_check(wd.type, (int) wd.K, (int) wd.N, T) == 0 && pm_mmq_i8_q80_tables((int) wd.K, st, &tab, &qb, &db) == 0) {
             pm_launch_silu_mul_q80_tab(m->h, m->h2, tab, qb, db, F, T, st);
-            return pm_launch_mmq_i8(wd.type, wd.d, nullptr, nullptr, x_next, (int) wd.K, (int) wd.N, T, nullptr, x_mid, 1, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: down mat-mul") : 0;
+            const pm_mmq_job down = mmq_job(wd, x_next, nullptr, x_mid);
+            return pm_launch_mmq_i8(&down, 1, {nullptr, nullptr, 1}, (int) wd.K, T, nullptr, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: down mat-mul") : 0;
         }
         if (gu_done) pm_launch_silu_mul(m->h, m->h2, m->h, (long) T * F, st);
         const Tensor * dn[1] = {&wd};
         a = quantize_for(m, m->h, F, T, dn, 1, st);
     }
-    prepped = false;
-    return matmul_small(m, wd, a, T, x_next, nullptr, x_mid, prepped, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: down gemv") : 0;
+    return matmul_small(m, wd, a, T, x_next, nullptr, x_mid, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: down gemv") : 0;
 }
 // small batches, T = 2 .. MMQ_MAX_TOKENS: the small-batch mat-mul (mmq_i8.hip) where it serves the types, else the multi-column mat-vec (mmvq_cols.hip)
 int layer_small(pm355_model * m, const Layer & L, int T, const float * cur, float * x_mid, float * x_next, hipStream_t st) {

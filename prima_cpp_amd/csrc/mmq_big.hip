@@ -361,7 +361,7 @@ __global__ __launch_bounds__(NTHR, 2) void mmq_big_kernel(BigP p) {
 
 } // namespace
 
-size_t pm_mmq_big_table_bytes(int K, int T) { return (size_t) ((T + 31) / 32) * (size_t) (K / 256) * (1024 + 128); }
+size_t pm_mmq_big_table_bytes(int K, int T) { return (size_t) ((T + 31) / 32) * pm_q8k_tab_bytes(K); }
 
 // 0 when pm_launch_mmq_big serves the shape
 int pm_mmq_big_check(int type, int K, int N, int T) {
@@ -383,7 +383,7 @@ int pm_launch_mmq_big(int type, const void * W, const void * xq, const void * ta
     BigP p = {};
     p.W = (const uint8_t *) W; p.row_stride = (long) pm_weight_row_stride(type, K); p.N = N; p.K = K; p.T = T;
     p.xq = (const uint8_t *) xq; p.xq_stride = (long) pm_q8k_row_bytes(K);
-    p.tab = (const uint8_t *) tab; p.tab_bytes = (long) (K / 256) * (1024 + 128); p.n_pass = (T + 31) / 32;
+    p.tab = (const uint8_t *) tab; p.tab_bytes = (long) pm_q8k_tab_bytes(K); p.n_pass = (T + 31) / 32;
     p.y = Y; p.y_stride = N; p.bias = bias; p.resid = resid;
     p.nt_t = (T + TM - 1) / TM;
     auto go = [&](auto kern, int tn, size_t lds) {
@@ -429,7 +429,7 @@ int pm_launch_mmq_big_f32(int type, const void * W, const float * X, float * Y, 
     const size_t tabs = (pm_mmq_big_table_bytes(K, T) + 255) & ~(size_t) 255, xrow = pm_q8k_row_bytes(K);
     uint8_t * sc = big_scratch(dev, st, tabs + (size_t) T * xrow + 256);
     if (!sc) return -3;
-    pm_q8k_tables tb; tb.base = sc; tb.tab_bytes = (size_t) (K / 256) * (1024 + 128); tb.nsb = K / 256;
+    const pm_q8k_tables tb = pm_q8k_tables_at(sc, K);
     if (!reuse_x) pm_launch_quantize_q8k(X, sc + tabs, K, T, st, tb);
     return pm_launch_mmq_big(type, W, sc + tabs, sc, Y, K, N, T, bias, resid, st);
 }

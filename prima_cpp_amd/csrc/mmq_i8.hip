@@ -41,12 +41,12 @@
 #include "pm355_kernels.h"
 #include <mutex>
 
-// what pm_launch_mmq_i8 serves: every quantized weight type has an MT<>
+// what pm_launch_mmq_i8's single form serves: every quantized weight type has an MT<>
 constexpr uint32_t MMQ_I8_TYPES = PM_QUANT_WEIGHTS;
-// ... and the several-matrices-of-one-type launch (pm_launch_mmq_i8_multi): instantiated for Q4_K and Q6_K only; Q5_K, Q8_0 and Q5_0 matrices
+// ... and its multi-job form (several matrices of one type): instantiated for Q4_K and Q6_K only; Q5_K, Q8_0 and Q5_0 matrices
 // answer -5 and go one launch each
 constexpr uint32_t MMQ_I8_MULTI_TYPES = pm_type_set(PM_Q4_K, PM_Q6_K);
-// ... and the two-type launch (pm_launch_mmq_i8_dual): Q4_K matrices next to one matrix of one of these (wq | wk + wv of the Q4_K_M files)
+// ... and its two-part grid: Q4_K matrices next to one matrix of one of these (wq | wk + wv of the Q4_K_M files)
 constexpr uint32_t MMQ_I8_DUAL_B_TYPES = pm_type_set(PM_Q6_K, PM_Q5_K);
 
 namespace {
@@ -690,22 +690,224 @@ __global__ __launch_bounds__(64) void mmq_prep_q80_kernel(const uint8_t * xq, lo
     if (g == 0) dT[blk * 32 + t] = t < T ? h2f(((const uint16_t *) (row + K))[blk]) : 0.0f;
 }
 
+// ---- host half. One of each: device lookup, scratch pool, table layout, MmqP builder, grid arithmetic, instantiation picker - and on top of them ONE launcher
+// (pm_launch_mmq_i8) whose comment is the routing between the three forms.
+
 // row groups a workgroup works on side by side (the other waves split K): 5..7 groups take all 8 wave slots in ONE round (one fill / drain of the step
 // pipeline, no K split) instead of two rounds of 4 (ffn_gate | ffn_up of the 70B shape: 7 groups per workgroup); PM355_MMQ_RGB8_MIN=8: the round-5 rule
 int rgb_log2_for(int nrg) {
     static const int rgb8_min = [] { const char * e = getenv("PM355_MMQ_RGB8_MIN"); const int v = e ? atoi(e) : 0; return v >= 3 && v <= 8 ? v : 5; }();
     return nrg >= rgb8_min ? 3 : nrg >= 3 ? 2 : nrg == 2 ? 1 : 0;
 }
+// `n` rows over `grid` workgroups: the 32-row groups of a workgroup's slice decide rgb_log2
+int rgb_log2_of(long n, int grid) { return rgb_log2_for(((int) ((n + grid - 1) / grid) + 31) / 32); }
+// one grid: a workgroup per CU, or per 32 rows where there are fewer of those
+int grid_for(long n, int cus) { return n / 32 >= cus ? cus : (int) ((n + 31) / 32); }
+// two-part grid: the device's workgroups divided by weight bytes; neither part gets more workgroups than it has 32-row groups. false: no workgroup left for part a
+bool dual_split(long na, size_t stride_a, int nb, size_t stride_b, int cus, int * ga, int * gb) {
+    const double bytes_a = (double) na * stride_a, bytes_b = (double) nb * stride_b;
+    int b = (int) (cus * bytes_b / (bytes_a + bytes_b) + 0.5);
+    b = b < 1 ? 1 : b;
+    if (b > (nb + 31) / 32) b = (nb + 31) / 32;
+    int a = cus - b;
+    if (a > (int) ((na + 31) / 32)) a = (int) ((na + 31) / 32);
+    *ga = a; *gb = b;
+    return a >= 1;
+}
 
-// per-device scratch (grown on demand, like mmq.hip's f16 activation copy): quantized activations of an f32 call + the two tables
-// scratch per (device, stream): the tables of a pass and the quantized copy of an f32 call are written and read in stream order, so two
-// streams of one device (two ggml backends, the engine next to the plug-in) must not share them
-struct Scr { hipStream_t st; uint8_t * p; size_t bytes; uint64_t use; int tab_K; };   // tab_K: the K the tables in p were last written for (0: none)
+// index of the current device in the per-device tables below, or -3 (no device, or beyond the 16 they hold)
+int mmq_dev() { int d = 0; return hipGetDevice(&d) == hipSuccess && d >= 0 && d < 16 ? d : -3; }
+
+// Scratch per (device, stream), grown on demand: the activation tables of two 32-token passes and the quantized copy of an f32 call are written and read
+// in stream order, so two streams of one device (two ggml backends, the engine next to the plug-in) must not share them. Two pools: the Q8_0 tables never
+// share bytes with the Q8_K tables a later launch may re-use.
+struct Scr { hipStream_t st; uint8_t * p; size_t bytes; uint64_t use; int tab_K; };   // tab_K: the K the tables in p were last handed out for (0: none)
 constexpr int NSCR = 8;
-Scr g_scr[16][NSCR] = {};
-Scr g_scr80[16][NSCR] = {};             // Q8_0 launches: their own tables (never share bytes with the Q8_K tables a later launch may re-use)
+Scr g_scr[2][16][NSCR] = {};           // [0] Q8_K, [1] Q8_0
 uint64_t g_tick = 0;
 std::mutex g_scr_mu;
+
+// THE layout of a scratch for K, written once. c: the 32-token pass (0, 1).
+//   Q8_K: pass 0 | pass 1 of {bsT: F16 group sums [nsb][64 lanes][8] | dT: scales [nsb][32]} | quantized copy of 64 f32 rows | ... at q_off, 256-aligned:
+//         pass 0 | pass 1 of qT, the values in A-operand order [nsb][8][64 lanes][16 B]
+//   Q8_0: pass 0 | pass 1 of {qT: the values [blk][64 lanes][16 B] | the f32 scales [blk][32] - what MmqP::bsT points to for these types} | 256 | quantized copy
+struct Tabs { uint8_t * bsT; float * dT; uint8_t * qT; uint8_t * xcopy; size_t bytes, qtab, dtab; };   // qtab / dtab: bytes of the Q8_0 pair per pass
+Tabs tabs_at(uint8_t * base, int K, int c, bool q80) {          // base == null: the size alone
+    size_t bs, d, q, xc;
+    Tabs t = {};
+    if (q80) {
+        const size_t qtab = (size_t) (K / 32) * 1024, dtab = (size_t) (K / 32) * 128;
+        q = c * (qtab + dtab); bs = d = q + qtab; xc = 2 * (qtab + dtab) + 256;
+        t.bytes = 2 * (qtab + dtab) + (size_t) 64 * pm_q80_row_bytes(K) + 512; t.qtab = qtab; t.dtab = dtab;
+    } else {
+        const size_t nsb = (size_t) (K / 256), tab = pm_q8k_tab_bytes(K);
+        const size_t q_off = ((2 * tab + (size_t) 64 * pm_q8k_row_bytes(K) + 256) + 255) & ~(size_t) 255;
+        bs = c * tab; d = bs + nsb * 1024; q = q_off + c * nsb * 8192; xc = 2 * tab;
+        t.bytes = q_off + 2 * nsb * 8192;
+    }
+    if (base) { t.bsT = base + bs; t.dT = (float *) (base + d); t.qT = base + q; t.xcopy = base + xc; }
+    return t;
+}
+
+// The scratch of (current device, stream st) for K out of its pool: the entry of the stream, else the least recently used one. null: no device, or the
+// allocation failed, or - lookup_only, a consumer that re-uses tables a producer wrote (pm_mmq_acts::tables_ready) - the entry of this stream no longer
+// exists (evicted by a ninth stream, re-allocated for a larger K in between) or does not hold tables for this K: the launch then fails instead of reading zeros.
+// A new allocation of the Q8_K pool is zeroed: table slots no quantizer ever wrote stay finite (they are multiplied by scale 0). ON THE OWNING STREAM: a
+// null-stream memset is not ordered against a non-blocking stream and zeroed the tables the first producer had just written (two ranks on one GPU,
+// tests/test_gpu_ring.py). The Q8_0 pool is not: its prologue writes every slot of a pass. tab_K is kept for both pools; the Q8_0 one is never looked up by it
+// (its consumer behind pm_launch_silu_mul_q80_tab takes the entry pm_mmq_i8_q80_tables just handed out).
+// hipMalloc / hipDeviceSynchronize on a launch path: ADVICE.md's finding about the prompt GEMM's scratch applies here as well (growth only, so a warmed-up
+// process never reaches them).
+Scr * scratch(bool q80, hipStream_t st, int K, bool lookup_only) {
+    const int dev = mmq_dev();
+    if (dev < 0) return nullptr;
+    const size_t need = tabs_at(nullptr, K, 0, q80).bytes;
+    std::lock_guard<std::mutex> lk(g_scr_mu);
+    Scr * e = nullptr, * lru = &g_scr[q80][dev][0];
+    for (Scr & c : g_scr[q80][dev]) {
+        if (c.p && c.st == st) { e = &c; break; }
+        if (!c.p) { if (lru->p) lru = &c; } else if (lru->p && c.use < lru->use) lru = &c;
+    }
+    if (lookup_only && (!e || e->tab_K != K || e->bytes < need)) return nullptr;
+    if (!e || e->bytes < need) {
+        if (!e) e = lru;
+        if (e->p) { (void) hipDeviceSynchronize(); (void) hipFree(e->p); e->p = nullptr; e->bytes = 0; }
+        if (hipMalloc((void **) &e->p, need) != hipSuccess) { e->p = nullptr; return nullptr; }
+        if (!q80) (void) hipMemsetAsync(e->p, 0, need, st);
+        e->st = st; e->bytes = need;
+    }
+    e->use = ++g_tick; e->tab_K = K;
+    return e;
+}
+
+// the prologue: activation tables of every 32-token pass from xq = T quantized rows (Q8_K, or Q8_0 for the Q8_0 family)
+void launch_prep(bool q80, const Scr * sc, const void * xq, int K, int T, hipStream_t st) {
+    const size_t xrow = q80 ? pm_q80_row_bytes(K) : pm_q8k_row_bytes(K);
+    for (int t0 = 0, c = 0; t0 < T; t0 += 32, ++c) {
+        const Tabs tb = tabs_at(sc->p, K, c, q80);
+        const uint8_t * xc = (const uint8_t *) xq + (size_t) t0 * xrow;
+        const int tn = T - t0 < 32 ? T - t0 : 32;
+        if (q80) hipLaunchKernelGGL(mmq_prep_q80_kernel, dim3(K / 32), dim3(64), 0, st, xc, (long) xrow, K, tn, tb.qT, tb.dT);
+        else     hipLaunchKernelGGL(mmq_prep_kernel, dim3(K / 256), dim3(64), 0, st, xc, (long) xrow, K, tn, tb.bsT, tb.dT, tb.qT);
+    }
+}
+
+// wq | wk | wv epilogue (MmqP::e_*): NORM-mode rope, transposed F16 V cache, engine mode (cell = position), whole heads
+bool epi_served(const pm_qkv_epi * e, const pm_mmq_job * j) {
+    return !(e->neox || e->v_rowmajor || e->dyn || !e->tab || !e->pos || !e->kc || !e->vc || e->dh < 2 || (e->dh & 1) || (e->n_rot & 1)) &&
+           j[0].N % e->dh == 0 && j[1].N == e->Hkv * e->dh && j[2].N == j[1].N;
+}
+
+// One MmqP: jobs [0, n) of one type as ONE virtual row space (slots >= n repeat the last job and start past the end), the pass (tokens t0 .. t0 + tn, tables
+// tb of its 32 token slots) and, with e, the epilogue - role0 + j = what job j is (1 q, 2 k, 3 v). The single-job fields are job 0's: the instantiations
+// without per-lane row pointers read those. (Fields no instantiation of the form reads are filled all the same - the single-job ones in a list, dT for the
+// Q8_0 family - and MmqP::xq / xq_stride stay 0: no kernel reads them, the activations come from the tables.)
+MmqP mmq_params(const pm_mmq_job * jobs, int n, int K, int t0, int tn, const Tabs & tb, int rgb_log2, const pm_qkv_epi * e, int role0) {
+    MmqP p = {};
+    p.row_stride = (long) pm_weight_row_stride(jobs[0].type, K); p.K = K; p.T = tn; p.t_off = t0 % 32; p.rgb_log2 = rgb_log2;
+    p.bsT = tb.bsT; p.dT = tb.dT; p.qT = tb.qT;
+    p.njobs = n;
+    for (int j = 0; j < 3; ++j) {
+        const pm_mmq_job & jb = jobs[j < n ? j : n - 1];
+        p.Wj[j] = (const uint8_t *) jb.W; p.yj[j] = jb.y + (size_t) t0 * jb.N; p.bj[j] = jb.bias; p.nj[j] = jb.N;
+        p.start[j] = p.N;
+        if (j < n) p.N += jb.N;
+        if (e) p.e_role[j] = j < n ? role0 + j : 0;
+    }
+    p.W = p.Wj[0]; p.y = p.yj[0]; p.y_stride = p.nj[0]; p.bias = p.bj[0];
+    p.resid = jobs[0].resid ? jobs[0].resid + (size_t) t0 * jobs[0].N : nullptr;       // (lists carry none)
+    if (e) {
+        p.e_on = 1; p.e_tab = e->tab; p.e_pos = e->pos; p.e_seq = e->seq; p.e_seq_stride = e->seq_stride; p.e_kc = (uint16_t *) e->kc; p.e_vc = (uint16_t *) e->vc;
+        p.e_dh = e->dh; p.e_nctx = e->n_ctx; p.e_nrot = e->n_rot; p.e_kvdim = e->Hkv * e->dh;
+    }
+    return p;
+}
+
+// The instantiations, named once. NV 16 (17..32 tokens) exists for Q4_K and Q6_K only (Q5_K: 11 weight registers more per step, its 32-token form spills
+// 388 B / lane; the Q8_0 family's spills 236 B: 502 vs 422 us per Qwen2.5-72B layer at 32 tokens - they take passes of 16); the multi-job form (per-lane row
+// pointers) for Q4_K and Q6_K; the epilogue only in that form. Q6_K, NV 8, one matrix: wave-uniform row addressing spills 44 B per lane, the multi-job form
+// does not (249 registers) - the launcher sends that case out as a list of ONE job.
+typedef void (*MmqKernel)(MmqP);
+typedef void (*MmqDualKernel)(MmqP2);
+template <int TYPE, bool MJ, bool EPI>
+MmqKernel mmq_kernel_nv(int nv) {
+    if (nv == 4) return mmq_i8_kernel<TYPE, 4, 0, MJ, EPI>;
+    if constexpr (TYPE != PM_Q6_K || MJ) if (nv == 8) return mmq_i8_kernel<TYPE, 8, 0, MJ, EPI>;
+    if constexpr (TYPE == PM_Q4_K || TYPE == PM_Q6_K) if (nv == 16) return mmq_i8_kernel<TYPE, 16, 0, MJ, EPI>;
+    return nullptr;
+}
+MmqKernel mmq_kernel(int type, int nv, bool mj, bool epi) {
+    if (mj) {
+        if (type == PM_Q4_K) return epi ? mmq_kernel_nv<PM_Q4_K, true, true>(nv) : mmq_kernel_nv<PM_Q4_K, true, false>(nv);
+        if (type == PM_Q6_K) return epi ? mmq_kernel_nv<PM_Q6_K, true, true>(nv) : mmq_kernel_nv<PM_Q6_K, true, false>(nv);
+        return nullptr;
+    }
+    if (epi) return nullptr;
+    switch (type) {
+        case PM_Q4_K: return mmq_kernel_nv<PM_Q4_K, false, false>(nv);
+        case PM_Q5_K: return mmq_kernel_nv<PM_Q5_K, false, false>(nv);
+        case PM_Q6_K: return mmq_kernel_nv<PM_Q6_K, false, false>(nv);
+        case PM_Q8_0: return mmq_kernel_nv<PM_Q8_0, false, false>(nv);
+        case PM_Q5_0: return mmq_kernel_nv<PM_Q5_0, false, false>(nv);
+    }
+    return nullptr;
+}
+template <int TB, bool EPI>
+MmqDualKernel mmq_dual_kernel_nv(int nv) {
+    if (nv == 4) return mmq_i8_dual_kernel<PM_Q4_K, TB, 4, EPI>;
+    if (nv == 8) return mmq_i8_dual_kernel<PM_Q4_K, TB, 8, EPI>;
+    if constexpr (TB == PM_Q6_K) if (nv == 16) return mmq_i8_dual_kernel<PM_Q4_K, TB, 16, EPI>;
+    return nullptr;
+}
+MmqDualKernel mmq_dual_kernel(int tb, int nv, bool epi) {
+    if (tb == PM_Q6_K) return epi ? mmq_dual_kernel_nv<PM_Q6_K, true>(nv) : mmq_dual_kernel_nv<PM_Q6_K, false>(nv);
+    if (tb == PM_Q5_K) return epi ? mmq_dual_kernel_nv<PM_Q5_K, true>(nv) : mmq_dual_kernel_nv<PM_Q5_K, false>(nv);
+    return nullptr;
+}
+template <typename P>
+void mmq_go(void (*kern)(P), int grid, size_t lds, hipStream_t st, const P & p) {
+    pm_allow_big_lds((const void *) kern, 150 * 1024);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, p);
+}
+
+// which form serves the list (pm_launch_mmq_i8's table), or the refusal. Host logic only: no device call
+int mmq_route(const pm_mmq_job * jobs, int njobs, int K, int T, bool epi, int * form) {
+    if (!jobs || njobs < 1 || njobs > 4) return -5;
+    if (njobs == 1) {
+        *form = PM_MMQ_SINGLE;
+        const int rc = pm_mmq_i8_check(jobs[0].type, K, jobs[0].N, T);
+        return rc ? rc : epi ? -5 : 0;
+    }
+    static const bool dual_off = [] { const char * e = getenv("PM355_MMQ_DUAL"); return e && e[0] == '0'; }();
+    const int t0 = jobs[0].type, tl = jobs[njobs - 1].type;
+    bool head_same = true;
+    for (int j = 1; j < njobs - 1; ++j) head_same = head_same && jobs[j].type == t0;
+    if (head_same && tl == t0 && njobs <= 3 && pm_in_set(MMQ_I8_MULTI_TYPES, t0) && T <= 64) *form = PM_MMQ_MULTI;
+    else if (!dual_off && head_same && t0 == PM_Q4_K && pm_in_set(MMQ_I8_DUAL_B_TYPES, tl) && T >= 1 && T <= (tl == PM_Q5_K ? 16 : 32)) *form = PM_MMQ_DUAL;
+    else return -5;
+    for (int j = 0; j < njobs; ++j) if (jobs[j].resid || pm_mmq_i8_check(jobs[j].type, K, jobs[j].N, T)) return -5;
+    return epi && (njobs != 3 || T > 32) ? -5 : 0;
+}
+// the launch geometry of a routed list on a device of `cus` CUs
+int mmq_geometry(int form, const pm_mmq_job * jobs, int njobs, int K, int T, int cus, pm_mmq_plan_t * pl) {
+    const int na = form == PM_MMQ_DUAL ? njobs - 1 : njobs, t0 = jobs[0].type;
+    long total = 0;
+    for (int j = 0; j < na; ++j) total += jobs[j].N;
+    int grid[2] = {0, 0}, rgb[2] = {0, 0};
+    if (form == PM_MMQ_DUAL) {
+        const pm_mmq_job & b = jobs[na];
+        if (!dual_split(total, pm_weight_row_stride(t0, K), b.N, pm_weight_row_stride(b.type, K), cus, &grid[0], &grid[1])) return -5;
+        rgb[1] = rgb_log2_of(b.N, grid[1]);
+    } else grid[0] = grid_for(total, cus);
+    rgb[0] = rgb_log2_of(total, grid[0]);
+    const int tmax = form == PM_MMQ_SINGLE && (t0 == PM_Q5_K || pm_q80_family(t0)) ? 16 : 32;
+    pl->npass = 0;
+    for (int s = 0; s < T; s += tmax) {
+        const int tn = T - s < tmax ? T - s : tmax;
+        pl->pass[pl->npass++] = {form, s, tn, tn <= 8 ? 4 : tn <= 16 ? 8 : 16, {grid[0], grid[1]}, {rgb[0], rgb[1]}};
+    }
+    return 0;
+}
 
 }  // namespace
 
@@ -716,7 +918,7 @@ size_t pm_mmq_i8_lds_bytes(int type, int K) {
     return (size_t) (K / 256 + 1) * 128 + NWAVE * w;
 }
 
-// 0 when pm_launch_mmq_i8 serves this shape
+// 0 when the single form of pm_launch_mmq_i8 serves this shape
 int pm_mmq_i8_check(int type, int K, int N, int T) {
     if (!pm_in_set(MMQ_I8_TYPES, type)) return -1;
     if (pm_q80_family(type)) return (T < 1 || T > 64 || K % 32 || K < 512 || N < 1) ? -2 : 0;
@@ -725,191 +927,97 @@ int pm_mmq_i8_check(int type, int K, int N, int T) {
     return 0;
 }
 
-// Y[t][n] = W[n,:] . x[t,:] (+bias[n]) (+resid[t][n]) for 1 <= T <= 64 tokens (passes of up to 32). xq: activations already in the library's row-SoA Q8_K
-// form (quantize.hip), or null and x_f32 [T][K] is quantized first. Y / resid token stride = N.
-namespace {
-// scratch of (device, stream) for K: tables of two 32-token passes + a quantized copy of up to 64 f32 rows; null: allocation failed (or,
-// lookup_only, no scratch of this stream holds tables for K)
-size_t scr_q_off(int K) { return ((2 * (size_t) (K / 256) * (1024 + 128) + (size_t) 64 * pm_q8k_row_bytes(K) + 256) + 255) & ~(size_t) 255; }
-Scr * scratch(int dev, hipStream_t st, int K, bool lookup_only) {
-    const size_t need = scr_q_off(K) + 2 * (size_t) (K / 256) * 8192;          // tables of two passes | quantized copy of 64 rows | operand-ordered values of two passes
-    std::lock_guard<std::mutex> lk(g_scr_mu);
-    Scr * e = nullptr, * lru = &g_scr[dev][0];
-    for (Scr & c : g_scr[dev]) {
-        if (c.p && c.st == st) { e = &c; break; }
-        if (!c.p) { if (lru->p) lru = &c; } else if (lru->p && c.use < lru->use) lru = &c;
-    }
-    // lookup_only (a consumer that re-uses tables a producer wrote): the entry of this stream must still exist (not evicted by a ninth
-    // stream, not re-allocated for a larger K in between) AND hold tables for this K - else the launch fails instead of reading zeros
-    if (lookup_only) {
-        if (!e || e->tab_K != K || e->bytes < need) return nullptr;
-        e->use = ++g_tick;
-        return e;
-    }
-    if (e && e->bytes >= need) { e->use = ++g_tick; e->tab_K = K; return e; }
-    if (!e) e = lru;
-    if (e->p) { (void) hipDeviceSynchronize(); (void) hipFree(e->p); e->p = nullptr; e->bytes = 0; }
-    if (hipMalloc((void **) &e->p, need) != hipSuccess) { e->p = nullptr; return nullptr; }
-    // table slots no quantizer ever wrote stay finite (they are multiplied by scale 0). ON THE OWNING STREAM: a null-stream memset is not ordered
-    // against a non-blocking stream and zeroed the tables the first producer had just written (two ranks on one GPU, tests/test_gpu_ring.py)
-    (void) hipMemsetAsync(e->p, 0, need, st);
-    e->st = st; e->bytes = need; e->use = ++g_tick; e->tab_K = K;
-    return e;
-}
-// activation tables of every 32-token pass
-void launch_prep(const Scr * sc, const void * xq, int K, int T, hipStream_t st) {
-    const int nsb = K / 256;
-    const size_t xrow = pm_q8k_row_bytes(K), tab = (size_t) nsb * (1024 + 128);
-    for (int t0 = 0, c = 0; t0 < T; t0 += 32, ++c) {
-        uint8_t * bsT = sc->p + c * tab;
-        hipLaunchKernelGGL(mmq_prep_kernel, dim3(nsb), dim3(64), 0, st, (const uint8_t *) xq + (size_t) t0 * xrow, (long) xrow, K, T - t0 < 32 ? T - t0 : 32,
-                           bsT, (float *) (bsT + (size_t) nsb * 1024), sc->p + scr_q_off(K) + (size_t) c * nsb * 8192);
-    }
-}
-}  // namespace
-
-namespace {
-// Q8_0 / Q5_0 weights x Q8_0 activations, passes of up to 16 tokens. xq: row-SoA Q8_0 rows (quantize.hip) or null and x_f32 is quantized first. Its tables
-// (operand-ordered values + f32 scales of both 32-slot halves, then a quantized copy of 64 f32 rows) are written by a prologue launch per call.
-Scr * scratch80(int dev, hipStream_t st, size_t need) {
-    std::lock_guard<std::mutex> lk(g_scr_mu);
-    Scr * e = nullptr, * lru = &g_scr80[dev][0];
-    for (Scr & c : g_scr80[dev]) {
-        if (c.p && c.st == st) { e = &c; break; }
-        if (!c.p) { if (lru->p) lru = &c; } else if (lru->p && c.use < lru->use) lru = &c;
-    }
-    if (!e || e->bytes < need) {
-        if (!e) e = lru;
-        if (e->p) { (void) hipDeviceSynchronize(); (void) hipFree(e->p); e->p = nullptr; e->bytes = 0; }
-        if (hipMalloc((void **) &e->p, need) != hipSuccess) { e->p = nullptr; return nullptr; }
-        e->st = st; e->bytes = need;
-    }
-    e->use = ++g_tick;
-    return e;
-}
-size_t q80_need(int K) { return 2 * ((size_t) (K / 32) * 1024 + (size_t) (K / 32) * 128) + (size_t) 64 * pm_q80_row_bytes(K) + 512; }
-
-// reuse_prep: the tables of this (device, stream) already describe these activations (pm_launch_silu_mul_q80_tab wrote them): no quantizer, no prologue launch
-int launch_q80(int type, const void * W, const void * xq, const float * x_f32, float * Y, int K, int N, int T, const float * bias, const float * resid, int reuse_prep, hipStream_t st) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-    const int nb = K / 32;
-    const size_t xrow = pm_q80_row_bytes(K), qtab = (size_t) nb * 1024, dtab = (size_t) nb * 128;
-    Scr * e = scratch80(dev, st, q80_need(K));
-    if (!e) return -3;
-    uint8_t * base = e->p;
-    if (!reuse_prep) {
-    if (!xq) {
-        uint8_t * q = base + 2 * (qtab + dtab) + 256;
-        pm_launch_quantize_q80(x_f32, q, K, T, st);
-        xq = q;
-    }
-    for (int t0 = 0, c = 0; t0 < T; t0 += 32, ++c)
-        hipLaunchKernelGGL(mmq_prep_q80_kernel, dim3(nb), dim3(64), 0, st, (const uint8_t *) xq + (size_t) t0 * xrow, (long) xrow, K, T - t0 < 32 ? T - t0 : 32,
-                           base + c * (qtab + dtab), (float *) (base + c * (qtab + dtab) + qtab));
-    }
-    const int cus = pm_device_cus();
-    const int grid = N / 32 >= cus ? cus : (N + 31) / 32;
-    const int rows = (N + grid - 1) / grid, nrg = (rows + 31) / 32;
-    const size_t lds = pm_mmq_i8_lds_bytes(type, K);
-    constexpr int tmax = 16;                         // (the 32-token form spills 236 B: 502 vs 422 us per Qwen2.5-72B layer at 32 tokens - two passes of 16 it is)
-    for (int t0 = 0; t0 < T; t0 += tmax) {
-        const int tn = T - t0 < tmax ? T - t0 : tmax;
-        uint8_t * tab = base + (t0 / 32) * (qtab + dtab);
-        MmqP p = {};
-        p.t_off = t0 % 32;
-        p.W = (const uint8_t *) W; p.row_stride = (long) pm_weight_row_stride(type, K); p.N = N; p.K = K; p.T = tn;
-        p.qT = tab; p.bsT = tab + qtab;                            // (bsT: here the f32 activation scales [blk][32])
-        p.y = Y + (size_t) t0 * N; p.y_stride = N; p.bias = bias; p.resid = resid ? resid + (size_t) t0 * N : nullptr;
-        p.rgb_log2 = rgb_log2_for(nrg);
-        auto go = [&](auto kern) {
-            pm_allow_big_lds((const void *) kern, 150 * 1024);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, p);
-        };
-        if (type == PM_Q5_0) { if (tn <= 8) go(mmq_i8_kernel<PM_Q5_0, 4>); else go(mmq_i8_kernel<PM_Q5_0, 8>); }
-        else                 { if (tn <= 8) go(mmq_i8_kernel<PM_Q8_0, 4>); else go(mmq_i8_kernel<PM_Q8_0, 8>); }
-    }
-    return 0;
-}
-}  // namespace
-
 // Q8_0 weights: where a producer (pm_launch_silu_mul_q80_tab) writes the activation tables of this (device, stream) for K; per 32-token pass qtab + dtab bytes
 int pm_mmq_i8_q80_tables(int K, hipStream_t st, void ** tab, size_t * qtab_bytes, size_t * dtab_bytes) {
     if (K % 32 || K < 512) return -2;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-    Scr * e = scratch80(dev, st, q80_need(K));
-    if (!e) return -3;
-    *tab = e->p; *qtab_bytes = (size_t) (K / 32) * 1024; *dtab_bytes = (size_t) (K / 32) * 128;
+    const Scr * sc = scratch(true, st, K, false);
+    if (!sc) return -3;
+    const Tabs t = tabs_at(sc->p, K, 0, true);
+    *tab = t.qT; *qtab_bytes = t.qtab; *dtab_bytes = t.dtab;
     return 0;
 }
 
 // Where the tables for K live: pm_launch_quantize_q8k / pm_launch_rmsnorm_q8k write them as a second output (<= 64 rows), the mat-mul is
-// then launched with reuse_prep = 1 and no prologue launch at all.
+// then launched with tables_ready and no prologue launch at all.
 int pm_mmq_i8_tables(int K, hipStream_t st, pm_q8k_tables * out) {
     if (K % 256 || K < 512) return -2;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-    const Scr * sc = scratch(dev, st, K, false);
+    const Scr * sc = scratch(false, st, K, false);
     if (!sc) return -3;
-    out->base = sc->p; out->nsb = K / 256; out->tab_bytes = (size_t) (K / 256) * (1024 + 128); out->qbase = sc->p + scr_q_off(K);
+    const Tabs t = tabs_at(sc->p, K, 0, false);
+    *out = pm_q8k_tables_at(t.bsT, K, t.qT);
     return 0;
 }
 
 // The prologue alone (tables for xq = T rows of row-SoA Q8_K): lets a caller fork streams between the prologue and several
-// pm_launch_mmq_i8(..., reuse_prep = 1, ...) launches that share the activations.
+// pm_launch_mmq_i8 launches with tables_ready that share the activations.
 int pm_launch_mmq_i8_prep(const void * xq, int K, int T, hipStream_t st) {
     if (T < 1 || T > 64 || K % 256 || K < 512) return -2;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-    const Scr * sc = scratch(dev, st, K, false);
+    const Scr * sc = scratch(false, st, K, false);
     if (!sc) return -3;
-    launch_prep(sc, xq, K, T, st);
+    launch_prep(false, sc, xq, K, T, st);
     return 0;
 }
 
-// reuse_prep != 0: the previous pm_launch_mmq_i8 / pm_launch_mmq_i8_prep on this device had the SAME activations (xq / x_f32 contents, T, K)
-// and is ordered before this launch: its quantized copy and tables are still valid, skip the prologue launches (q/k/v and gate/up share
-// one activation set).
-int pm_launch_mmq_i8(int type, const void * W, const void * xq, const float * x_f32, float * Y, int K, int N, int T,
-                     const float * bias, const float * resid, int reuse_prep, hipStream_t st) {
-    const int rc = pm_mmq_i8_check(type, K, N, T);
-    if (rc) return rc;
-    if (pm_q80_family(type)) return launch_q80(type, W, xq, x_f32, Y, K, N, T, bias, resid, reuse_prep, st);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-    const int nsb = K / 256;
-    const size_t xrow = pm_q8k_row_bytes(K), tab = (size_t) nsb * (1024 + 128);
-    const Scr * sc = scratch(dev, st, K, reuse_prep != 0);
+int pm_mmq_i8_plan(const pm_mmq_job * jobs, int njobs, int K, int T, int epi, int cus, pm_mmq_plan_t * out) {
+    int form = 0;
+    const int rc = mmq_route(jobs, njobs, K, T, epi != 0, &form);
+    return rc ? rc : mmq_geometry(form, jobs, njobs, K, T, cus, out);
+}
+
+// y_j[t][n] = W_j[n,:] . x[t,:] (+ bias_j[n]) (+ resid_j[t][n]) for the matrices of `jobs` over ONE set of 1 <= T <= 64 activation rows; y / resid token
+// stride = N_j. x.xq: the rows in the library's row-SoA form (quantize.hip: Q8_K; Q8_0 for the Q8_0 family), or null and x.f32 [T][K] is quantized first into the
+// scratch. x.tables_ready: the activation tables of this (device, stream) already describe these rows - a quantizer wrote them as its second output
+// (pm_mmq_i8_tables, pm_mmq_i8_q80_tables), or an earlier call / pm_launch_mmq_i8_prep over the SAME activations is ordered before this one (q / k / v and
+// gate / up share one set): no quantizer, no prologue launch.
+//
+// The form is chosen from the list alone:
+//   single       one job, any type of MMQ_I8_TYPES, T <= 64 in passes of 32 (Q5_K and the Q8_0 family: 16). Q6_K with 9..16 tokens in a pass goes out in the
+//                multi-job instantiation, as a list of one.
+//   multi-job    2..3 jobs of one type in MMQ_I8_MULTI_TYPES (wq | wk | wv, ffn_gate | ffn_up): one virtual row space, one fill / drain of the step pipeline
+//                instead of two or three (~10 us each). T <= 64 in passes of 32.
+//   two-part     1..3 Q4_K jobs and a last job of a type in MMQ_I8_DUAL_B_TYPES (wq | wk + wv of the Q4_K_M files) as ONE grid (mmq_i8_dual_kernel): the
+//                device's workgroups are divided by weight bytes. One pass: T <= 32 (Q5_K: 16). PM355_MMQ_DUAL=0 turns it off.
+// A list no form serves answers -5 and the caller splits it: nothing here falls back launch by launch. Lists carry no resid (-5). epi: RoPE + KV store in the
+// epilogue of a wq, wk, wv list (three jobs in that order, NORM rope, T <= 32, whole heads, epi_served); given and not served: -5.
+// 0, or for one job -1 type / -2 shape / -4 LDS; -3 device or scratch (tables_ready: no tables for this K on this stream); -5.
+int pm_launch_mmq_i8(const pm_mmq_job * jobs, int njobs, pm_mmq_acts x, int K, int T, const pm_qkv_epi * epi, hipStream_t st) {
+    int form = 0;
+    if (const int rc = mmq_route(jobs, njobs, K, T, epi != nullptr, &form)) return rc;
+    if (epi && !epi_served(epi, jobs)) return -5;
+    const bool q80 = pm_q80_family(jobs[0].type);
+    // (Q8_0 family: its tables are re-used only straight behind pm_launch_silu_mul_q80_tab, whose pm_mmq_i8_q80_tables has just handed out this entry)
+    const Scr * sc = scratch(q80, st, K, x.tables_ready && !q80);
     if (!sc) return -3;
-    if (!xq) {
-        uint8_t * q = sc->p + 2 * tab;
-        if (!reuse_prep) pm_launch_quantize_q8k(x_f32, q, K, T, st);
-        xq = q;
+    if (!x.tables_ready) {
+        const void * xq = x.xq;
+        if (!xq) {
+            uint8_t * q = tabs_at(sc->p, K, 0, q80).xcopy;
+            if (q80) pm_launch_quantize_q80(x.f32, q, K, T, st); else pm_launch_quantize_q8k(x.f32, q, K, T, st);
+            xq = q;
+        }
+        launch_prep(q80, sc, xq, K, T, st);
     }
-    if (!reuse_prep) launch_prep(sc, xq, K, T, st);
-    const int cus = pm_device_cus();
-    const int grid = N / 32 >= cus ? cus : (N + 31) / 32;
-    const int rows = (N + grid - 1) / grid, nrg = (rows + 31) / 32;
-    const size_t lds = pm_mmq_i8_lds_bytes(type, K);
-    const int tmax = type == PM_Q5_K ? 16 : 32;                    // (Q5_K: 11 weight registers more per step - its 32-token form spills 388 B / lane)
-    for (int t0 = 0, c = 0; t0 < T; t0 += tmax, ++c) {
-        const int tn = T - t0 < tmax ? T - t0 : tmax;
-        uint8_t * bsT = sc->p + (t0 / 32) * tab; float * dT = (float *) (bsT + (size_t) nsb * 1024);    // tables are per 32 tokens
-        const uint8_t * xc = (const uint8_t *) xq + (size_t) t0 * xrow;
-        MmqP p = {};
-        p.t_off = t0 % 32;
-        p.W = (const uint8_t *) W; p.row_stride = (long) pm_weight_row_stride(type, K); p.N = N; p.K = K; p.T = tn;
-        p.xq = xc; p.xq_stride = (long) xrow; p.bsT = bsT; p.dT = dT; p.qT = sc->p + scr_q_off(K) + (size_t) (t0 / 32) * nsb * 8192;
-        p.y = Y + (size_t) t0 * N; p.y_stride = N; p.bias = bias; p.resid = resid ? resid + (size_t) t0 * N : nullptr;
-        p.rgb_log2 = rgb_log2_for(nrg);
-        auto go = [&](auto kern) {
-            pm_allow_big_lds((const void *) kern, 150 * 1024);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, p);
-        };
+    pm_mmq_plan_t pl;
+    if (const int rc = mmq_geometry(form, jobs, njobs, K, T, pm_device_cus(), &pl)) return rc;
+    for (int i = 0; i < pl.npass; ++i) {
+        const pm_mmq_pass & ps = pl.pass[i];
+        const Tabs tb = tabs_at(sc->p, K, ps.t0 / 32, q80);                // (tables are per 32 tokens: a 16-token pass is half of one, MmqP::t_off)
+        if (form == PM_MMQ_DUAL) {
+            const pm_mmq_job * b = jobs + njobs - 1;
+            const MmqP2 pp = {mmq_params(jobs, njobs - 1, K, ps.t0, ps.tn, tb, ps.rgb_log2[0], epi, 1),
+                              mmq_params(b, 1, K, ps.t0, ps.tn, tb, ps.rgb_log2[1], epi, njobs), ps.grid[0]};
+            const size_t la = pm_mmq_i8_lds_bytes(jobs[0].type, K), lb = pm_mmq_i8_lds_bytes(b->type, K);
+            const MmqDualKernel kern = mmq_dual_kernel(b->type, ps.nv, epi != nullptr);
+            if (!kern) return -5;                                          // (not reached: mmq_route admits what is instantiated)
+            mmq_go(kern, ps.grid[0] + ps.grid[1], la > lb ? la : lb, st, pp);
+            continue;
+        }
+        const int type = jobs[0].type, tn = ps.tn;
+        const MmqP p = mmq_params(jobs, njobs, K, ps.t0, tn, tb, ps.rgb_log2[0], epi, 1);
+        auto go = [&](auto kern) { mmq_go<MmqP>(kern, ps.grid[0], pm_mmq_i8_lds_bytes(type, K), st, p); };
 #ifdef PM_MMQ_ABLATE      // measurement build (profiles/r02_small_batch_probe.txt): PM355_MMQ_ABL = 1 no activation loads | 2 no weight loads | 4 no compute
         static const int abl = [] { const char * e = getenv("PM355_MMQ_ABL"); return e ? atoi(e) : 0; }();
-        if (abl && tn <= 8) {
+        if (abl && tn <= 8 && form == PM_MMQ_SINGLE && !q80) {
 #define PM_ABL_CASE(T_) switch (abl) { case 1: go(mmq_i8_kernel<T_, 4, 1>); break; case 2: go(mmq_i8_kernel<T_, 4, 2>); break; case 3: go(mmq_i8_kernel<T_, 4, 3>); break; \
                                        case 4: go(mmq_i8_kernel<T_, 4, 4>); break; case 5: go(mmq_i8_kernel<T_, 4, 5>); break; case 6: go(mmq_i8_kernel<T_, 4, 6>); break; \
                                        default: go(mmq_i8_kernel<T_, 4, 7>); break; }
@@ -917,150 +1025,11 @@ int pm_launch_mmq_i8(int type, const void * W, const void * xq, const float * x_
 #undef PM_ABL_CASE
         } else
 #endif
-        if (type == PM_Q4_K) { if (tn <= 8) go(mmq_i8_kernel<PM_Q4_K, 4>); else if (tn <= 16) go(mmq_i8_kernel<PM_Q4_K, 8>); else go(mmq_i8_kernel<PM_Q4_K, 16>); }
-        else if (type == PM_Q5_K) { if (tn <= 8) go(mmq_i8_kernel<PM_Q5_K, 4>); else go(mmq_i8_kernel<PM_Q5_K, 8>); }
-        else if (tn <= 8)    go(mmq_i8_kernel<PM_Q6_K, 4>);
-        else if (tn <= 16) {
-            // the 16-token Q6_K form with wave-uniform row addressing spills 44 B per lane; the one with per-lane row pointers (the multi-job form) does not
-            // (249 registers): a launch of ONE job in that form
-            p.njobs = 1; p.y_stride = N;
-            for (int j = 0; j < 3; ++j) { p.Wj[j] = p.W; p.yj[j] = p.y; p.bj[j] = p.bias; p.nj[j] = N; p.start[j] = j == 0 ? 0 : N; }
-            go(mmq_i8_kernel<PM_Q6_K, 8, 0, true>);
+        {
+            const MmqKernel kern = mmq_kernel(type, ps.nv, form == PM_MMQ_MULTI || (type == PM_Q6_K && ps.nv == 8), epi != nullptr);
+            if (!kern) return -5;                                          // (not reached: mmq_route admits what is instantiated)
+            go(kern);
         }
-        else                 go(mmq_i8_kernel<PM_Q6_K, 16>);
     }
-    return 0;
-}
-
-namespace {
-// wq | wk | wv epilogue of a launch (MmqP::e_*): NORM-mode rope, transposed F16 V cache, engine mode (cell = position). false: not served
-bool fill_epi(MmqP & p, const pm_qkv_epi * e, int r0, int r1, int r2) {
-    if (!e) return true;
-    if (e->neox || e->v_rowmajor || e->dyn || !e->tab || !e->pos || !e->kc || !e->vc || e->dh < 2 || (e->dh & 1) || (e->n_rot & 1)) return false;
-    p.e_on = 1; p.e_role[0] = r0; p.e_role[1] = r1; p.e_role[2] = r2;
-    p.e_tab = e->tab; p.e_pos = e->pos; p.e_seq = e->seq; p.e_seq_stride = e->seq_stride; p.e_kc = (uint16_t *) e->kc; p.e_vc = (uint16_t *) e->vc;
-    p.e_dh = e->dh; p.e_nctx = e->n_ctx; p.e_nrot = e->n_rot; p.e_kvdim = e->Hkv * e->dh;
-    return true;
-}
-}  // namespace
-
-// Up to 3 matrices of ONE type and K sharing the activations (wq | wk | wv, ffn_gate | ffn_up) in one launch: one fill / drain of the
-// step pipeline instead of two or three (~10 us each). T <= 64 in passes of 32 (round 4: with the operand-ordered activation table the 32-token
-// instantiations have the registers for per-lane row pointers: 238 / 250 VGPRs); -5: not served, launch the jobs one by one. y[j]: [T][N[j]].
-int pm_launch_mmq_i8_multi(int type, int njobs, const void * const * W, const int * N, float * const * Y, const float * const * bias, const void * xq,
-                           int K, int T, int reuse_prep, hipStream_t st, const pm_qkv_epi * epi) {
-    if (njobs < 2 || njobs > 3 || T > 64 || !pm_in_set(MMQ_I8_MULTI_TYPES, type)) return -5;
-    // epi: the jobs are wq, wk, wv (three jobs, one pass, even row counts whose heads are whole)
-    if (epi && (njobs != 3 || T > 32 || N[0] % epi->dh || N[1] != epi->Hkv * epi->dh || N[2] != N[1])) return -5;
-    long total = 0;
-    for (int j = 0; j < njobs; ++j) { if (pm_mmq_i8_check(type, K, N[j], T)) return -5; total += N[j]; }
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-    const int nsb = K / 256;
-    const size_t xrow = pm_q8k_row_bytes(K);
-    const Scr * sc = scratch(dev, st, K, reuse_prep != 0);
-    if (!sc) return -3;
-    if (!reuse_prep) launch_prep(sc, xq, K, T, st);
-    const int cus = pm_device_cus();
-    const int grid = total / 32 >= cus ? cus : (int) ((total + 31) / 32);
-    const int rows = (int) ((total + grid - 1) / grid), nrg = (rows + 31) / 32;
-    MmqP p = {};
-    p.row_stride = (long) pm_weight_row_stride(type, K); p.N = (int) total; p.K = K; p.T = T;
-    p.xq = (const uint8_t *) xq; p.xq_stride = (long) xrow; p.bsT = sc->p; p.dT = (const float *) (sc->p + (size_t) nsb * 1024); p.qT = sc->p + scr_q_off(K);
-    p.njobs = njobs;
-    int at = 0;
-    for (int j = 0; j < 3; ++j) {
-        const int jj = j < njobs ? j : njobs - 1;
-        p.Wj[j] = (const uint8_t *) W[jj]; p.yj[j] = Y[jj]; p.bj[j] = bias ? bias[jj] : nullptr; p.nj[j] = N[jj];
-        p.start[j] = j < njobs ? at : (int) total;
-        if (j < njobs) at += N[j];
-    }
-    p.rgb_log2 = rgb_log2_for(nrg);
-    if (!fill_epi(p, epi, 1, 2, 3)) return -5;
-    const size_t lds = pm_mmq_i8_lds_bytes(type, K);
-    auto go = [&](auto kern) {
-        pm_allow_big_lds((const void *) kern, 150 * 1024);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, st, p);
-    };
-    const size_t tab = (size_t) nsb * (1024 + 128);
-    for (int t0 = 0, c = 0; t0 < T; t0 += 32, ++c) {                 // passes of 32 tokens, each with its own tables
-        const int tn = T - t0 < 32 ? T - t0 : 32;
-        p.T = tn;
-        p.bsT = sc->p + c * tab; p.dT = (const float *) (p.bsT + (size_t) nsb * 1024); p.qT = sc->p + scr_q_off(K) + (size_t) c * nsb * 8192;
-        for (int j = 0; j < 3; ++j) { const int jj = j < njobs ? j : njobs - 1; p.yj[j] = Y[jj] + (size_t) t0 * N[jj]; }
-        if (p.e_on && type == PM_Q4_K) { if (tn <= 8) go(mmq_i8_kernel<PM_Q4_K, 4, 0, true, true>); else if (tn <= 16) go(mmq_i8_kernel<PM_Q4_K, 8, 0, true, true>); else go(mmq_i8_kernel<PM_Q4_K, 16, 0, true, true>); }
-        else if (p.e_on)         { if (tn <= 8) go(mmq_i8_kernel<PM_Q6_K, 4, 0, true, true>); else if (tn <= 16) go(mmq_i8_kernel<PM_Q6_K, 8, 0, true, true>); else go(mmq_i8_kernel<PM_Q6_K, 16, 0, true, true>); }
-        else if (type == PM_Q4_K) { if (tn <= 8) go(mmq_i8_kernel<PM_Q4_K, 4, 0, true>); else if (tn <= 16) go(mmq_i8_kernel<PM_Q4_K, 8, 0, true>); else go(mmq_i8_kernel<PM_Q4_K, 16, 0, true>); }
-        else                 { if (tn <= 8) go(mmq_i8_kernel<PM_Q6_K, 4, 0, true>); else if (tn <= 16) go(mmq_i8_kernel<PM_Q6_K, 8, 0, true>); else go(mmq_i8_kernel<PM_Q6_K, 16, 0, true>); }
-    }
-    return 0;
-}
-
-// wq | wk (na matrices of type ta = Q4_K, as in pm_launch_mmq_i8_multi) AND one matrix of another K-quant type (wv: Q6_K / Q5_K) over the same activations as
-// ONE grid (mmq_i8_dual_kernel): the device's workgroups are divided by weight bytes. T <= 32 (Q5_K: 16) - one pass; -5: not served, launch them separately.
-int pm_launch_mmq_i8_dual(int ta, int na, const void * const * Wa, const int * Na, float * const * Ya, const float * const * ba,
-                          int tb, const void * Wb, int Nb, float * Yb, const float * bb, const void * xq, int K, int T, int reuse_prep, hipStream_t st,
-                          const pm_qkv_epi * epi) {
-    static const bool off = [] { const char * e = getenv("PM355_MMQ_DUAL"); return e && e[0] == '0'; }();
-    if (off || ta != PM_Q4_K || !pm_in_set(MMQ_I8_DUAL_B_TYPES, tb) || na < 1 || na > 3 || T < 1 || T > (tb == PM_Q5_K ? 16 : 32)) return -5;
-    long total = 0;
-    for (int j = 0; j < na; ++j) { if (pm_mmq_i8_check(ta, K, Na[j], T)) return -5; total += Na[j]; }
-    if (pm_mmq_i8_check(tb, K, Nb, T)) return -5;
-    // epi: part a = wq, wk; part b = wv
-    if (epi && (na != 2 || Na[0] % epi->dh || Na[1] != epi->Hkv * epi->dh || Nb != Na[1])) return -5;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -3;
-    const int nsb = K / 256;
-    const size_t xrow = pm_q8k_row_bytes(K);
-    const Scr * sc = scratch(dev, st, K, reuse_prep != 0);
-    if (!sc) return -3;
-    if (!reuse_prep) launch_prep(sc, xq, K, T, st);
-    const int cus = pm_device_cus();
-    const double bytes_a = (double) total * pm_weight_row_stride(ta, K), bytes_b = (double) Nb * pm_weight_row_stride(tb, K);
-    int gb = (int) (cus * bytes_b / (bytes_a + bytes_b) + 0.5);
-    gb = gb < 1 ? 1 : gb;
-    if (gb > (Nb + 31) / 32) gb = (Nb + 31) / 32;
-    int ga = cus - gb;
-    if (ga > (int) ((total + 31) / 32)) ga = (int) ((total + 31) / 32);
-    if (ga < 1) return -5;
-    MmqP2 pp = {};
-    {
-        MmqP & p = pp.a;
-        p.row_stride = (long) pm_weight_row_stride(ta, K); p.N = (int) total; p.K = K; p.T = T;
-        p.xq = (const uint8_t *) xq; p.xq_stride = (long) xrow; p.bsT = sc->p; p.dT = (const float *) (sc->p + (size_t) nsb * 1024); p.qT = sc->p + scr_q_off(K);
-        p.njobs = na;
-        int at = 0;
-        for (int j = 0; j < 3; ++j) {
-            const int jj = j < na ? j : na - 1;
-            p.Wj[j] = (const uint8_t *) Wa[jj]; p.yj[j] = Ya[jj]; p.bj[j] = ba ? ba[jj] : nullptr; p.nj[j] = Na[jj];
-            p.start[j] = j < na ? at : (int) total;
-            if (j < na) at += Na[j];
-        }
-        const int rows = (int) ((total + ga - 1) / ga);
-        p.rgb_log2 = rgb_log2_for((rows + 31) / 32);
-    }
-    {
-        MmqP & p = pp.b;
-        p.W = (const uint8_t *) Wb; p.row_stride = (long) pm_weight_row_stride(tb, K); p.N = Nb; p.K = K; p.T = T;
-        p.xq = (const uint8_t *) xq; p.xq_stride = (long) xrow; p.bsT = pp.a.bsT; p.dT = pp.a.dT; p.qT = pp.a.qT;
-        p.y = Yb; p.y_stride = Nb; p.bias = bb;
-        p.njobs = 1;
-        for (int j = 0; j < 3; ++j) { p.Wj[j] = p.W; p.yj[j] = Yb; p.bj[j] = bb; p.nj[j] = Nb; p.start[j] = j == 0 ? 0 : Nb; }
-        const int rows = (Nb + gb - 1) / gb;
-        p.rgb_log2 = rgb_log2_for((rows + 31) / 32);
-    }
-    pp.ga = ga;
-    if (!fill_epi(pp.a, epi, 1, 2, 0) || !fill_epi(pp.b, epi, 3, 0, 0)) return -5;
-    const size_t la = pm_mmq_i8_lds_bytes(ta, K), lb = pm_mmq_i8_lds_bytes(tb, K), lds = la > lb ? la : lb;
-    auto go = [&](auto kern) {
-        pm_allow_big_lds((const void *) kern, 150 * 1024);
-        hipLaunchKernelGGL(kern, dim3(ga + gb), dim3(BLOCK), lds, st, pp);
-    };
-    if (epi) {
-        if (tb == PM_Q6_K) { if (T <= 8) go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q6_K, 4, true>); else if (T <= 16) go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q6_K, 8, true>); else go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q6_K, 16, true>); }
-        else               { if (T <= 8) go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q5_K, 4, true>); else go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q5_K, 8, true>); }
-    }
-    else if (tb == PM_Q6_K) { if (T <= 8) go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q6_K, 4>); else if (T <= 16) go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q6_K, 8>); else go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q6_K, 16>); }
-    else               { if (T <= 8) go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q5_K, 4>); else go(mmq_i8_dual_kernel<PM_Q4_K, PM_Q5_K, 8>); }
     return 0;
 }

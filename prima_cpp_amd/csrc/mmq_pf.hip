@@ -205,7 +205,7 @@ __device__ __forceinline__ void pf_body(const PfP & p, const PfJob & jb, const i
         uint32_t v[2];
         half2v t[4];
         if (Q8) {
-            // int8 x -> byte x ^ 0x80 = x + 128 -> F16 1024 + 128 + x (exact) -> - 1152 -> * d: one rounding, dequantize_row_q8_0's d * x (ggml-quants.c:1616)
+            // int8 x -> byte x ^ 0x80 = x + 128 -> F16 1152 + x (exact) -> - 1152 -> * d: one rounding, dequantize_row_q8_0's d * x (ggml-quants.c:1616)
             const half2v bias = half2v{(_Float16) -1152.0f, (_Float16) -1152.0f};
 #pragma unroll
             for (int c = 0; c < 2; ++c) v[c] = w.ql[c] ^ 0x80808080u;

@@ -45,9 +45,12 @@ int pm_gemv_units_per_row(int type, int64_t K);
 // [super-block][32-value sub-block s][operand lane = 32 * (k / 16 % 2) + row % 32][16 bytes]: one coalesced load per sub-block instead of one
 // cache line per token
 struct pm_q8k_tables { uint8_t * base = nullptr; size_t tab_bytes = 0; int nsb = 0; uint8_t * qbase = nullptr; };
+// bytes of one 32-row pass of the first two tables: per 256-value super-block 64 lanes x 8 F16 sums | 32 f32 scales
+static inline size_t pm_q8k_tab_bytes(int K) { return (size_t) (K / 256) * (1024 + 128); }
+static inline pm_q8k_tables pm_q8k_tables_at(void * base, int K, void * qbase = nullptr) { return {(uint8_t *) base, pm_q8k_tab_bytes(K), K / 256, (uint8_t *) qbase}; }
 void pm_launch_quantize_q8k(const float * x, void * y, int K, int rows, hipStream_t st, pm_q8k_tables tab = {});
 void pm_launch_quantize_q80(const float * x, void * y, int K, int rows, hipStream_t st);
-// silu(gate) * up -> Q8_0, written into the Q8_0 small-batch mat-mul's activation tables (pm_mmq_i8_q80_tables); then pm_launch_mmq_i8(PM_Q8_0, ..., reuse_prep = 1)
+// silu(gate) * up -> Q8_0, written into the Q8_0 small-batch mat-mul's activation tables (pm_mmq_i8_q80_tables); then pm_launch_mmq_i8 with tables_ready
 void pm_launch_silu_mul_q80_tab(const float * gate, const float * up, void * tab, size_t qtab_bytes, size_t dtab_bytes, int K, int rows, hipStream_t st);
 int pm_mmq_i8_q80_tables(int K, hipStream_t st, void ** tab, size_t * qtab_bytes, size_t * dtab_bytes);
 // Q8_K rows of silu(gate) * up (the ffn_down activations of a small batch), no f32 product in HBM
@@ -127,19 +130,21 @@ int pm_launch_gemm_pf_ex(const pm_gemm_job * jobs, int njobs, const void * xh, i
 int pm_device_cus();
 struct pm_rope_cfg;
 
-// small-batch (1..32 tokens) quantized mat-mul on the integer matrix cores (mmq_i8.hip): Q4_K / Q6_K weights, Q8_K activations
-// (xq row-SoA, or x_f32 quantized first into a per-device scratch). 0, or -1 type / -2 shape / -3 device / -4 LDS
-int pm_mmq_i8_check(int type, int K, int N, int T);
-int pm_mmq_i8_tables(int K, hipStream_t st, pm_q8k_tables * out);      // where a quantizer writes the tables for K (<= 64 rows); then reuse_prep = 1
-int pm_launch_mmq_i8_prep(const void * xq, int K, int T, hipStream_t st);      // the activation tables alone (then reuse_prep = 1)
-int pm_launch_mmq_i8(int type, const void * W, const void * xq, const float * x_f32, float * Y, int K, int N, int T,
-                     const float * bias, const float * resid, int reuse_prep, hipStream_t st);
-// 2 or 3 matrices of one type and K that share the activations, as one launch (T <= 16); -5: not served, launch them one by one
-int pm_launch_mmq_i8_multi(int type, int njobs, const void * const * W, const int * N, float * const * Y, const float * const * bias, const void * xq,
-                           int K, int T, int reuse_prep, hipStream_t st, const pm_qkv_epi * epi = nullptr);
-int pm_launch_mmq_i8_dual(int ta, int na, const void * const * Wa, const int * Na, float * const * Ya, const float * const * ba,
-                          int tb, const void * Wb, int Nb, float * Yb, const float * bb, const void * xq, int K, int T, int reuse_prep, hipStream_t st,
-                          const pm_qkv_epi * epi = nullptr);  // epi: RoPE + KV store in the launch's epilogue (NORM rope, transposed V, T <= 32)
+// small-batch (1..64 tokens) quantized mat-mul on the integer matrix cores (mmq_i8.hip): quantized weights x Q8_K activations (Q8_0 / Q5_0 weights: Q8_0
+// activations). ONE entry over a job list - the routing between its three forms (single, multi-job, two-part grid) is written at pm_launch_mmq_i8
+// (mmq_i8.hip). 0, or -1 type / -2 shape / -4 LDS (one job), -3 device or scratch, -5 a list (or epilogue) no form serves: the caller splits it
+struct pm_mmq_job  { int type; int N; const void * W; float * y; const float * bias; const float * resid; };
+struct pm_mmq_acts { const void * xq; const float * f32; int tables_ready; };   // xq: quantized rows, or null and f32 [T][K]; tables_ready: no prologue launch
+int pm_launch_mmq_i8(const pm_mmq_job * jobs, int njobs, pm_mmq_acts x, int K, int T, const pm_qkv_epi * epi, hipStream_t st);
+int pm_mmq_i8_check(int type, int K, int N, int T);                    // 0 when ONE job of this shape is served
+int pm_mmq_i8_tables(int K, hipStream_t st, pm_q8k_tables * out);      // where a quantizer writes the tables for K (<= 64 rows); then tables_ready = 1
+int pm_launch_mmq_i8_prep(const void * xq, int K, int T, hipStream_t st);      // the activation tables alone (then tables_ready = 1)
+// the launcher's own arithmetic for a list on a device of `cus` CUs, host only: per pass the form, the tokens, the result registers per lane of the
+// instantiation (NV: 4 / 8 / 16) and grid / rgb_log2 of each part ([1]: part b of the two-part grid, else 0). 0, or the launcher's refusal
+enum { PM_MMQ_SINGLE = 0, PM_MMQ_MULTI = 1, PM_MMQ_DUAL = 2 };
+struct pm_mmq_pass { int form, t0, tn, nv, grid[2], rgb_log2[2]; };
+struct pm_mmq_plan_t { int npass; pm_mmq_pass pass[4]; };
+int pm_mmq_i8_plan(const pm_mmq_job * jobs, int njobs, int K, int T, int epi, int cus, pm_mmq_plan_t * out);
 
 // prompt-sized batches (>= 128 tokens) on the integer matrix cores (mmq_big.hip): Q4_K / Q6_K weights x Q8_K activations, the CPU reference's
 // integer arithmetic. xq = T rows of row-SoA Q8_K, tab = the activation tables a quantizer wrote for them (pm_q8k_tables{tab, (K / 256) * 1152, K / 256};

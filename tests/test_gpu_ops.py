@@ -316,6 +316,41 @@ def test_small_batch_matmul_wv_of_another_type_in_the_same_grid(P, oracle, tv):
         P.mul_mat_small_mixed(ws, xq, 40)
 
 
+@pytest.fixture(scope="module")
+def min_k_jobs(oracle):
+    """K = 512, the smallest the small-batch mat-mul serves: ONE step pair, so of the waves that split K over a row group all but one get no pair. Three
+    matrices whose 32-row groups straddle both job boundaries (96 | 34 | 34), the last one also as Q6_K and Q5_K; 33 activation rows; the oracle's products."""
+    rng = np.random.default_rng(512)
+    K, Ns = 512, (96, 34, 34)
+    x = rng.normal(0, 1, (33, K)).astype(np.float32)
+    blocks = {(t, j): rand_blocks(t, N, K, rng) for j, N in enumerate(Ns) for t in ((Q4_K, Q6_K) if j < 2 else (Q4_K, Q5_K, Q6_K))}
+    biases = [rng.normal(0, 1, N).astype(np.float32) for N in Ns]
+    want = {k: oracle.mul_mat(k[0], b, K, Ns[k[1]], x) + biases[k[1]][None] for k, b in blocks.items()}
+    return K, Ns, x, blocks, biases, want
+
+
+@pytest.mark.parametrize("types,T", [((Q4_K, Q4_K, Q4_K), 5), ((Q6_K, Q6_K, Q6_K), 5), ((Q4_K, Q4_K, Q6_K), 9), ((Q4_K, Q4_K, Q5_K), 9), ((Q4_K, Q4_K), 33), ((Q6_K, Q6_K), 33)],
+                         ids=["three_q4k", "three_q6k", "q6k_last_9_tokens", "q5k_last_9_tokens", "two_q4k_33_tokens", "two_q6k_33_tokens"])
+def test_small_batch_matmul_forms_at_the_smallest_k(P, min_k_jobs, types, T):
+    """The three forms of the small-batch launch at K = 512 (min_k_jobs): the three-job list; the same list with a Q6_K (Q5_K) last job at 9 tokens - the
+    two-part grid, whose part b then is the one-job multi-job instantiation (Q5_K: the single-matrix one); a two-job list at 33 tokens - a second pass with ONE
+    live token at table slot 0. Every job equals its own single-matrix launch (same integers, f32 sums of K / 256 = 2 terms) within 1e-5 and the oracle within
+    the mat-vec's tolerance (2e-5, absolute part scaled by sqrt(K / 4096) as in the tests above)."""
+    K, Ns, x, blocks, biases, want = min_k_jobs
+    n = len(types)
+    ws = [P.upload_weight(t, blocks[(t, j)], K, Ns[j]) for j, t in enumerate(types)]
+    xq = P.quantize_act(_dev(P, x[:T]), P.vec_dot_act_type(Q4_K))
+    bd = [_dev(P, b) for b in biases[:n]]
+    ys = P.mul_mat_small_multi(ws, xq, T, biases=bd) if len(set(types)) == 1 else P.mul_mat_small_mixed(ws, xq, T, biases=bd)
+    for j, (t, w, y) in enumerate(zip(types, ws, ys)):
+        got = y.cpu().numpy()
+        one = P.mul_mat_small(w, xq=xq, n_tokens=T, bias=bd[j]).cpu().numpy()
+        print(f"job {j} (type {t}, N {Ns[j]}, T {T}): max |fused - single| {np.abs(got - one).max():.2e}, max |fused - oracle| {np.abs(got - want[(t, j)][:T]).max():.2e}")
+        assert got.shape == (T, Ns[j]) and np.isfinite(got).all()
+        assert np.allclose(got, one, rtol=1e-5, atol=1e-5)
+        assert np.allclose(got, want[(t, j)][:T], rtol=2e-5, atol=2e-5 * np.sqrt(K / 4096))
+
+
 def test_rms_norm_matches_oracle(P, oracle):
     rng = np.random.default_rng(26)
     for K, eps in ((4096, 1e-5), (8192, 1e-6)):

@@ -200,3 +200,32 @@ def test_small_batch_rope_and_kv_store_in_the_qkv_epilogue_same_bits(E, tv, T, m
     for a, b in zip(*outs):
         assert torch.isfinite(a).all()
         assert torch.equal(a, b)
+
+
+def test_small_batch_tables_reused_across_wq_wk_and_then_wv_alone(E, monkeypatch):
+    """A 20-token step through layers whose wv is Q5_K next to Q4_K wq / wk (K = 512): the two-part grid refuses it (Q5_K: 16 tokens), so wq | wk go out as one
+    multi-job launch and wv alone, in two passes of 16 and 4 tokens over the SAME activation tables (tables_ready: no prologue launch in between; the second pass
+    reads table slots 16..19). Same tokens, and hidden rows / logits at the distance of PM355_NO_MMQ_I8=1 - which sends 20 tokens to the F16 prompt GEMM, so the
+    bound is that tier's (test_model_shaped_layer_decode_and_prefill (2), (3b): NMSE 5e-4 hidden, 1e-3 logits); the next single token reads the cache the step wrote."""
+    torch = E.torch
+    rng = np.random.default_rng(2020)
+    d = tiny_model(rng, arch=0, n_layer=2, n_embd=512, n_head=4, n_head_kv=2, n_ff=1024, n_vocab=320, n_ctx=64,
+                   types={"attn_v": Q5_K, "ffn_down": Q6_K, "output": Q6_K})
+    toks = rng.integers(0, d.n_vocab, 21).astype(np.int32)
+    outs = []
+    for off in ("0", "1"):
+        monkeypatch.setenv("PM355_NO_MMQ_I8", off)
+        w = E.Window(_hp(d), n_ctx=64)
+        w.load_desc(d)
+        w.finalize(max_tokens=32)
+        hb, lb, ab = w.decode(tokens=torch.from_numpy(toks[:20]).cuda(), pos0=0, want_argmax=True)
+        h1, l1, a1 = w.decode(tokens=torch.from_numpy(toks[20:]).cuda(), pos0=20, want_argmax=True)
+        outs.append([t.cpu().numpy().copy() for t in (hb, lb, ab, h1, l1, a1)])
+        w.close()
+    (hb, lb, ab, h1, l1, a1), (hb0, lb0, ab0, h10, l10, a10) = outs
+    f, g = _nmse(hb, hb0), _nmse(lb, lb0)
+    f1, g1 = _nmse(h1, h10), _nmse(l1, l10)
+    print(f"\n20-token step vs PM355_NO_MMQ_I8=1: hidden NMSE {f:.2e}, logits NMSE {g:.2e}; next token: hidden {f1:.2e}, logits {g1:.2e}")
+    assert np.isfinite(hb).all() and np.isfinite(lb).all()
+    assert np.array_equal(ab, ab0) and np.array_equal(a1, a10)
+    assert f < 5e-4 and g < 1e-3 and f1 < 5e-4 and g1 < 1e-3

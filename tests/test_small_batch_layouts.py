@@ -176,7 +176,7 @@ def test_epilogue_thread_finds_its_pair_in_the_neighbouring_lane():
 
 
 def dual_split(total_a, stride_a, Nb, stride_b, cus=256):
-    """pm_launch_mmq_i8_dual: the device's workgroups divided by weight bytes; neither part gets more workgroups than it has 32-row groups."""
+    """the two-part grid of pm_launch_mmq_i8 (dual_split, mmq_i8.hip): the device's workgroups divided by weight bytes; neither part gets more workgroups than it has 32-row groups."""
     ba, bb = total_a * stride_a, Nb * stride_b
     gb = int(cus * bb / (ba + bb) + 0.5)
     gb = max(gb, 1)
@@ -194,3 +194,114 @@ def test_two_part_grid_gives_every_part_workgroups_and_whole_row_groups(Na, Nb, 
         # the 70B shape: wq | wk take the bulk, wv (1024 rows) about one workgroup per 32 rows (Q6_K: 35.7 by bytes, capped at 32; Q5_K: 31)
         if (Na, Nb, K) == (9216, 1024, 8192):
             assert (ga, gb) == ((224, 32) if stride_b == K // 256 * 210 else (225, 31))
+
+
+# ---- the launch geometry of the small-batch mat-mul (pm_mmq_i8_plan, mmq_i8.hip: the arithmetic the launcher itself uses), checked against the rules of the
+# three launchers it replaced, restated here from their source: the geometry did not move when they became one
+
+Q5_0, Q8_0, Q4_K, Q5_K, Q6_K = 6, 8, 12, 13, 14
+SINGLE, MULTI, DUAL = 0, 1, 2
+
+
+def rgb_log2_for(nrg):
+    """row groups a workgroup works on side by side: 8 from 5 groups on, 4 from 3, else the group count"""
+    return 3 if nrg >= 5 else 2 if nrg >= 3 else 1 if nrg == 2 else 0
+
+
+def one_grid(N, cus):
+    """single and multi-job launches: a workgroup per CU, or per 32 rows where there are fewer; rgb_log2 from the 32-row groups of a workgroup's slice"""
+    grid = cus if N // 32 >= cus else (N + 31) // 32
+    return grid, rgb_log2_for(((N + grid - 1) // grid + 31) // 32)
+
+
+def part_rgb(N, grid):
+    return rgb_log2_for(((N + grid - 1) // grid + 31) // 32)
+
+
+def passes(T, tmax):
+    """(first token, tokens, result registers per lane: 4 up to 8 tokens, 8 up to 16, else 16)"""
+    return [(t0, min(T - t0, tmax), 4 if min(T - t0, tmax) <= 8 else 8 if min(T - t0, tmax) <= 16 else 16) for t0 in range(0, T, tmax)]
+
+
+def _plan(lib, types, Ns, K, T, epi=0, cus=256):
+    import ctypes as C
+    f = lib.pm355_mul_mat_q_small_plan
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    n = len(types)
+    ts, ns, out = (C.c_int * n)(*types), (C.c_int64 * n)(*Ns), (C.c_int32 * 32)()
+    rc = f(ts, ns, n, K, T, epi, cus, out, 4)
+    return rc if rc < 0 else [tuple(out[8 * i:8 * i + 8]) for i in range(rc)]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import ctypes as C
+    import prima_cpp_amd
+    lib = prima_cpp_amd.load()
+    lib.pm355_row_stride.restype = C.c_size_t
+    lib.pm355_row_stride.argtypes = [C.c_int, C.c_int64]
+    return lib
+
+
+# (K, N): this file's shapes, and the large matrices of a Llama-3-70B / Qwen2.5-72B layer (E 8192, wk / wv 1024, n_ff 28672 / 29568, Q8_0 ffn_down K = 29568)
+LAYER_KN = [(8192, 8192), (8192, 1024), (8192, 28672), (28672, 8192), (8192, 29568), (29568, 8192)]
+SMALL_KN = [(1024, 70), (1024, 75), (1024, 300), (2048, 2100), (4096, 1024), (5120, 5120), (512, 34), (768, 600), (1024, 20000)]
+TOKENS = [1, 2, 8, 9, 16, 17, 20, 32, 33, 48, 49, 64]
+
+
+@pytest.mark.parametrize("cus", [256, 64])
+def test_single_matrix_plan_is_the_former_launchers_arithmetic(lib, cus):
+    n = 0
+    for t in (Q4_K, Q5_K, Q6_K, Q8_0, Q5_0):
+        for K, N in LAYER_KN + SMALL_KN:
+            if K % 256 and t not in (Q8_0, Q5_0):
+                continue
+            grid, rgb = one_grid(N, cus)
+            tmax = 16 if t in (Q5_K, Q8_0, Q5_0) else 32               # (Q5_K and the Q8_0 family: their 32-token forms spill)
+            for T in TOKENS:
+                want = [(SINGLE, t0, tn, nv, grid, rgb, 0, 0) for t0, tn, nv in passes(T, tmax)]
+                assert _plan(lib, [t], [N], K, T, cus=cus) == want, (t, K, N, T)
+                assert all(nv <= 8 for _, _, _, nv, *_ in want) or t in (Q4_K, Q6_K)      # no 16-register form for Q5_K, Q8_0, Q5_0
+                n += 1
+    assert n > 500
+
+
+@pytest.mark.parametrize("cus", [256, 64])
+def test_multi_job_plan_is_the_former_launchers_arithmetic(lib, cus):
+    lists = [(8192, (8192, 1024, 1024)), (8192, (28672, 28672)), (8192, (29568, 29568)), (1024, (300, 70, 75)), (768, (2100, 2100)), (4096, (515, 40)),
+             (512, (96, 34, 34)), (768, (600, 600, 90))]
+    for t in (Q4_K, Q6_K):
+        for K, Ns in lists:
+            grid, rgb = one_grid(sum(Ns), cus)
+            for T in TOKENS:
+                want = [(MULTI, t0, tn, nv, grid, rgb, 0, 0) for t0, tn, nv in passes(T, 32)]
+                assert _plan(lib, [t] * len(Ns), Ns, K, T, cus=cus) == want, (t, K, Ns, T)
+                if len(Ns) == 3:                                       # the epilogue: three jobs, one pass
+                    assert _plan(lib, [t] * 3, Ns, K, T, epi=1, cus=cus) == (want if T <= 32 else -1)
+    # what no form serves is refused, not split: Q5_K / Q8_0 lists, four jobs of one type, a list past 64 tokens, an epilogue on two jobs
+    assert _plan(lib, [Q5_K] * 2, (64, 64), 1024, 8) == -1 and _plan(lib, [Q8_0] * 2, (64, 64), 1024, 8) == -1
+    assert _plan(lib, [Q4_K] * 4, (64,) * 4, 1024, 8) == -1 and _plan(lib, [Q4_K] * 2, (64, 64), 1024, 65) == -1
+    assert _plan(lib, [Q4_K] * 2, (64, 64), 1024, 8, epi=1) == -1 and _plan(lib, [Q6_K, Q6_K, Q4_K], (64,) * 3, 1024, 8) == -1
+
+
+@pytest.mark.parametrize("cus", [256, 64])
+def test_two_part_plan_is_the_former_launchers_arithmetic(lib, cus):
+    lists = [(8192, (8192, 1024), 1024), (4096, (4096, 1024), 1024), (5120, (5120, 1024), 1024), (1024, (300, 70), 75), (2048, (2100, 260), 300),
+             (512, (96, 34), 34), (8192, (1024,), 128), (1024, (64, 64, 64), 90)]
+    for tb in (Q6_K, Q5_K):
+        for K, Na, Nb in lists:
+            ga, gb = dual_split(sum(Na), lib.pm355_row_stride(Q4_K, K), Nb, lib.pm355_row_stride(tb, K), cus)
+            assert ga >= 1 and gb >= 1 and ga + gb <= cus
+            for T in TOKENS:
+                got = _plan(lib, [Q4_K] * len(Na) + [tb], list(Na) + [Nb], K, T, cus=cus)
+                if T > (16 if tb == Q5_K else 32):
+                    assert got == -1, (tb, K, Na, Nb, T)               # one pass only
+                    continue
+                (t0, tn, nv), = passes(T, 32)
+                assert got == [(DUAL, t0, tn, nv, ga, part_rgb(sum(Na), ga), gb, part_rgb(Nb, gb))], (tb, K, Na, Nb, T)
+                if len(Na) == 2:
+                    assert _plan(lib, [Q4_K, Q4_K, tb], list(Na) + [Nb], K, T, epi=1, cus=cus) == got
+    # the 70B layer on 256 CUs: wq | wk take the bulk, wv (1024 rows) about one workgroup per 32 rows
+    assert _plan(lib, [Q4_K, Q4_K, Q6_K], [8192, 1024, 1024], 8192, 8)[0][4:] == (224, 1, 32, 0)
+    assert _plan(lib, [Q4_K, Q4_K, Q5_K], [8192, 1024, 1024], 8192, 8)[0][4:] == (225, 1, 31, 1)
