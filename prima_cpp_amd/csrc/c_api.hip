@@ -147,16 +147,37 @@ int pm355_rms_norm(const float * x, const float * w, float * y, void * yq, int64
     return 0;
 }
 
-static int gemv_rc(int rc) {
-    switch (rc) {
-        case 0: return 0;
-        case -1: return fail(PM355_E_UNSUPPORTED, "mul_mat_vec_q: weight type");
-        case -2: return fail(PM355_E_SHAPE, "mul_mat_vec_q: K not a multiple of the block size");
-        case -3: return fail(PM355_E_ALIGN, "mul_mat_vec_q: K not a multiple of 32 for Q8_0");
-        case -4: return fail(PM355_E_RANGE, "mul_mat_vec_q: K too large");
-        case -8: return fail(PM355_E_UNSUPPORTED, "mul_mat_vec_q: sum-of-squares partials / attention tail are built into libprima_mi355_exp.so only (PM_EXPERIMENTS)");
-        default: return fail(PM355_E_HIP, "mul_mat_vec_q: launch", hipGetLastError());
-    }
+// The mat-vec launchers' return codes (pm355_kernels.h) as the C ABI's, for every mat-vec entry. -5, -6 and -7 have a text with the entry that can ask for what they
+// refuse and are a failed launch elsewhere (as is the job count, -9: every entry checks or fixes it first); the epilogue check answers -5 without a text
+enum { MV_ANY, MV_SS, MV_QKV, MV_QKV_CHECK };
+static const struct { int rc, entry, code; const char * text; } GEMV_RC[] = {
+    {-1, MV_ANY, PM355_E_UNSUPPORTED, "mul_mat_vec_q: weight type"},
+    {-2, MV_ANY, PM355_E_SHAPE, "mul_mat_vec_q: K not a multiple of the block size"},
+    {-3, MV_ANY, PM355_E_ALIGN, "mul_mat_vec_q: K not a multiple of 32 for Q8_0"},
+    {-4, MV_ANY, PM355_E_RANGE, "mul_mat_vec_q: K too large"},
+    {-5, MV_QKV_CHECK, PM355_E_UNSUPPORTED, nullptr},
+    {-5, MV_QKV, PM355_E_UNSUPPORTED, "mul_mat_vec_qkv: every workgroup's row slices must hold whole rotation pairs (N % (2 * CUs) == 0), N_k == N_v == n_head_kv * head_dim"},
+    {-6, MV_SS, PM355_E_UNSUPPORTED, "mul_mat_vec_fused_ss: sumsq_out needs ONE plain job; sumsq_in needs norm_w and 1..256 partials"},
+    {-7, MV_QKV, PM355_E_UNSUPPORTED, "mul_mat_vec_qkv_attn: the workgroups of a KV-head group must be a power-of-two run of the grid (CUs % n_head_kv == 0), head_dim 64 / 128, position-pointer mode, transposed V cache"},
+    {-8, MV_ANY, PM355_E_UNSUPPORTED, "mul_mat_vec_q: sum-of-squares partials / attention tail are built into libprima_mi355_exp.so only (PM_EXPERIMENTS)"},
+};
+static int gemv_rc(int rc, int entry = MV_ANY) {
+    if (rc == 0) return 0;
+    for (const auto & r : GEMV_RC) if (r.rc == rc && (r.entry == MV_ANY || r.entry == entry)) return r.text ? fail(r.code, r.text) : r.code;
+    return fail(PM355_E_HIP, "mul_mat_vec_q: launch", hipGetLastError());
+}
+// a job list of the C ABI as the launcher's; qkv: wq | wk | wv for the epilogue entries - three plain jobs whatever the caller left in W2 / resid
+static pm_gemv_fused fused_of(const pm355_matvec_job * jobs, int njobs, int64_t K, const float * x, const float * norm_w, float eps, bool qkv = false) {
+    pm_gemv_fused f = {};
+    f.K = (int) K; f.njobs = qkv ? 3 : njobs; f.xf = x; f.norm_w = norm_w; f.eps = eps;
+    for (int j = 0; j < f.njobs; ++j) f.job[j] = {jobs[j].type, (int) jobs[j].N, jobs[j].W, qkv ? nullptr : jobs[j].W2, jobs[j].y, jobs[j].bias, qkv ? nullptr : jobs[j].resid};
+    return f;
+}
+static pm_qkv_epi qkv_epi_of(const pm355_qkv_store & s) {
+    pm_qkv_epi e = {};
+    e.tab = s.rope_table; e.pos = s.d_pos; e.dyn = s.d_cell_nkv; e.kc = s.k_cache; e.vc = s.v_cache;
+    e.Hkv = s.n_head_kv; e.dh = s.head_dim; e.n_ctx = s.n_ctx; e.n_rot = s.n_rot; e.v_rowmajor = s.v_rowmajor; e.neox = s.rope_neox;
+    return e;
 }
 // pm_launch_gemm's return codes (pm355_kernels.h); what = the entry's name
 static int gemm_rc(int rc, const char * what) {
@@ -177,33 +198,15 @@ int pm355_mul_mat_vec_q(int type, const void * W, const void * W2, int64_t K, in
 int pm355_mul_mat_vec_fused(const pm355_matvec_job * jobs, int njobs, int64_t K, const float * x_f32, const float * norm_w,
                             float eps, pm355_stream_t st) {
     if (njobs < 1 || njobs > 3 || !jobs || !x_f32) return fail(PM355_E_RANGE, "mul_mat_vec_fused: 1..3 jobs and an f32 activation");
-    pm_gemv_fused f = {};
-    f.K = (int) K; f.njobs = njobs; f.xf = x_f32; f.norm_w = norm_w; f.eps = eps;
-    for (int j = 0; j < njobs; ++j) {
-        f.job[j].type = jobs[j].type; f.job[j].N = (int) jobs[j].N; f.job[j].W = jobs[j].W; f.job[j].W2 = jobs[j].W2;
-        f.job[j].y = jobs[j].y; f.job[j].bias = jobs[j].bias; f.job[j].resid = jobs[j].resid;
-    }
-    (void) hipGetLastError();
-    const int rc = gemv_rc(pm_launch_gemv_fused(f, S(st)));
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return pm355_mul_mat_vec_fused_ss(jobs, njobs, K, x_f32, norm_w, eps, nullptr, nullptr, 0, st);
 }
 int pm355_mul_mat_vec_fused_ss(const pm355_matvec_job * jobs, int njobs, int64_t K, const float * x_f32, const float * norm_w, float eps,
                                double * sumsq_out, const double * sumsq_in, int n_sumsq_in, pm355_stream_t st) {
     if (njobs < 1 || njobs > 3 || !jobs || !x_f32) return fail(PM355_E_RANGE, "mul_mat_vec_fused_ss: 1..3 jobs and an f32 activation");
-    pm_gemv_fused f = {};
-    f.K = (int) K; f.njobs = njobs; f.xf = x_f32; f.norm_w = norm_w; f.eps = eps;
+    pm_gemv_fused f = fused_of(jobs, njobs, K, x_f32, norm_w, eps);
     f.ss_out = sumsq_out; f.ss_in = sumsq_in; f.n_ss = n_sumsq_in;
-    for (int j = 0; j < njobs; ++j) {
-        f.job[j].type = jobs[j].type; f.job[j].N = (int) jobs[j].N; f.job[j].W = jobs[j].W; f.job[j].W2 = jobs[j].W2;
-        f.job[j].y = jobs[j].y; f.job[j].bias = jobs[j].bias; f.job[j].resid = jobs[j].resid;
-    }
     (void) hipGetLastError();
-    const int lrc = pm_launch_gemv_fused(f, S(st));
-    if (lrc == -8) return gemv_rc(-8);
-    if (lrc == -6) return fail(PM355_E_UNSUPPORTED, "mul_mat_vec_fused_ss: sumsq_out needs ONE plain job; sumsq_in needs norm_w and 1..256 partials");
-    const int rc = gemv_rc(lrc);
+    const int rc = gemv_rc(pm_launch_gemv_fused(f, S(st)), MV_SS);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
@@ -234,18 +237,12 @@ int pm355_q6k_tail_grouped(void) { return PM_Q6K_SCD ? 1 : 0; }
 int pm355_experiments_built(void) { return PM_EXPERIMENTS ? 1 : 0; }
 int pm355_mul_mat_vec_fused_grid(const pm355_matvec_job * jobs, int njobs, int64_t K) {
     if (njobs < 1 || njobs > 3 || !jobs) return fail(PM355_E_RANGE, "mul_mat_vec_fused_grid: 1..3 jobs");
-    pm_gemv_fused f = {};
-    f.K = (int) K; f.njobs = njobs; f.xf = (const float *) 16;
-    for (int j = 0; j < njobs; ++j) { f.job[j].type = jobs[j].type; f.job[j].N = (int) jobs[j].N; f.job[j].W = jobs[j].W; f.job[j].W2 = jobs[j].W2; }
-    const int g = pm_gemv_fused_grid(f);
-    return g > 0 ? g : gemv_rc(g);
+    pm_gemv_plan pl; const int rc = pm_gemv_fused_plan(fused_of(jobs, njobs, K, (const float *) 16, nullptr, 0.0f), 0, pl);
+    return rc ? gemv_rc(rc) : pl.grid;
 }
 int pm355_mul_mat_vec_fused_check(const pm355_matvec_job * jobs, int njobs, int64_t K) {
     if (njobs < 1 || njobs > 3 || !jobs) return fail(PM355_E_RANGE, "mul_mat_vec_fused: 1..3 jobs");
-    pm_gemv_fused f = {};
-    f.K = (int) K; f.njobs = njobs; f.xf = (const float *) 16;
-    for (int j = 0; j < njobs; ++j) { f.job[j].type = jobs[j].type; f.job[j].N = (int) jobs[j].N; f.job[j].W = jobs[j].W; f.job[j].W2 = jobs[j].W2; }
-    return gemv_rc(pm_gemv_fused_check(f));
+    pm_gemv_plan pl; return gemv_rc(pm_gemv_fused_plan(fused_of(jobs, njobs, K, (const float *) 16, nullptr, 0.0f), 0, pl));
 }
 int pm355_mul_mat_q_mfma(int type, const void * W, int64_t K, int64_t N, const float * x, int64_t n_tokens, float * y,
                          const float * bias, const float * resid, pm355_stream_t st) {
@@ -455,15 +452,9 @@ int pm355_mul_mat_vec_qkv_ss(const pm355_matvec_job * jobs, int64_t K, const flo
 int pm355_mul_mat_vec_qkv_attn(const pm355_matvec_job * jobs, int64_t K, const float * x_f32, const float * norm_w, float eps,
                                const pm355_qkv_store * s, const double * sumsq_in, int n_sumsq_in, const pm355_qkv_attn * at, pm355_stream_t st) {
     if (!jobs || !x_f32 || !s || !s->rope_table || !s->k_cache || !s->v_cache || (!s->d_pos && !s->d_cell_nkv)) return fail(PM355_E_SHAPE, "mul_mat_vec_qkv: null pointer");
-    pm_gemv_fused f = {};
-    f.K = (int) K; f.njobs = 3; f.xf = x_f32; f.norm_w = norm_w; f.eps = eps;
+    pm_gemv_fused f = fused_of(jobs, 3, K, x_f32, norm_w, eps, true);
     if (sumsq_in && n_sumsq_in > 0 && norm_w) { f.ss_in = sumsq_in; f.n_ss = n_sumsq_in; }
-    for (int j = 0; j < 3; ++j) {
-        f.job[j].type = jobs[j].type; f.job[j].N = (int) jobs[j].N; f.job[j].W = jobs[j].W; f.job[j].W2 = nullptr;
-        f.job[j].y = jobs[j].y; f.job[j].bias = jobs[j].bias; f.job[j].resid = nullptr;
-    }
-    pm_qkv_epi e = {s->rope_table, s->d_pos, nullptr, s->d_cell_nkv, 0, s->k_cache, s->v_cache, s->n_head_kv, s->head_dim, s->n_ctx, s->n_rot,
-                    s->v_rowmajor, s->rope_neox};
+    pm_qkv_epi e = qkv_epi_of(*s);
     if (at) {
         if (!at->out || !at->ticket) return fail(PM355_E_SHAPE, "mul_mat_vec_qkv_attn: null pointer");
         e.att_out = at->out; e.att_ticket = at->ticket; e.att_err = at->watchdog; e.kq_scale = at->kq_scale; e.n_head = at->n_head; e.att_max_keys = at->max_keys;
@@ -471,10 +462,7 @@ int pm355_mul_mat_vec_qkv_attn(const pm355_matvec_job * jobs, int64_t K, const f
     f.epi = &e;
     (void) hipGetLastError();
     const int rc = pm_launch_gemv_fused(f, S(st));
-    if (rc == -8) return gemv_rc(-8);
-    if (rc == -7) return fail(PM355_E_UNSUPPORTED, "mul_mat_vec_qkv_attn: the workgroups of a KV-head group must be a power-of-two run of the grid (CUs % n_head_kv == 0), head_dim 64 / 128, position-pointer mode, transposed V cache");
-    if (rc == -5) return fail(PM355_E_UNSUPPORTED, "mul_mat_vec_qkv: every workgroup's row slices must hold whole rotation pairs (N % (2 * CUs) == 0), N_k == N_v == n_head_kv * head_dim");
-    if (rc) return gemv_rc(rc);
+    if (rc) return gemv_rc(rc, MV_QKV);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -487,18 +475,13 @@ int pm355_engine_run(const pm355_engine_phase * phs, int n, pm355_stream_t st) {
         const pm355_engine_phase & e = phs[i];
         if (e.kind == 0) {
             if (e.njobs < 1 || e.njobs > 3 || !e.jobs || !e.x_f32) { rc = -100; break; }
-            pm_gemv_fused f = {};
-            f.K = (int) e.K; f.njobs = e.njobs; f.xf = e.x_f32; f.norm_w = e.norm_w; f.eps = e.eps;
+            pm_gemv_fused f = fused_of(e.jobs, e.njobs, e.K, e.x_f32, e.norm_w, e.eps);
             f.ss_out = e.sumsq_out; f.ss_in = e.sumsq_in; f.n_ss = e.n_sumsq_in;
-            for (int j = 0; j < e.njobs; ++j) {
-                f.job[j].type = e.jobs[j].type; f.job[j].N = (int) e.jobs[j].N; f.job[j].W = e.jobs[j].W; f.job[j].W2 = e.jobs[j].W2;
-                f.job[j].y = e.jobs[j].y; f.job[j].bias = e.jobs[j].bias; f.job[j].resid = e.jobs[j].resid;
-            }
             pm_qkv_epi qe = {};
             if (e.qkv) {
                 const pm355_qkv_store * s = e.qkv;
                 if (s->d_cell_nkv || !s->d_pos || e.njobs != 3) { rc = -100; break; }
-                qe = pm_qkv_epi{s->rope_table, s->d_pos, nullptr, nullptr, 0, s->k_cache, s->v_cache, s->n_head_kv, s->head_dim, s->n_ctx, s->n_rot, s->v_rowmajor, s->rope_neox};
+                qe = qkv_epi_of(*s);
                 f.epi = &qe;
             }
             rc = pm_eng_plan_add_matvec(pl, f);
@@ -524,13 +507,30 @@ int pm355_engine_run(const pm355_engine_phase *, int, pm355_stream_t) { return f
 #endif
 int pm355_mul_mat_vec_qkv_check_ex(const pm355_matvec_job * jobs, int64_t K, int n_head_kv, int head_dim, int n_rot, int rope_neox) {
     if (!jobs) return fail(PM355_E_SHAPE, "mul_mat_vec_qkv_check: jobs");
-    pm_gemv_fused f = {};
-    f.K = (int) K; f.njobs = 3; f.xf = (const float *) 16;
-    for (int j = 0; j < 3; ++j) { f.job[j].type = jobs[j].type; f.job[j].N = (int) jobs[j].N; f.job[j].W = jobs[j].W; f.job[j].bias = jobs[j].bias; }
-    const pm_qkv_epi e = {(const float *) 16, (const int32_t *) 16, nullptr, nullptr, 0, (void *) 16, (void *) 16, n_head_kv, head_dim, 8, n_rot, 0, rope_neox ? 1 : 0};
+    pm_gemv_fused f = fused_of(jobs, 3, K, (const float *) 16, nullptr, 0.0f, true);
+    pm_qkv_epi e = {};
+    e.tab = (const float *) 16; e.pos = (const int32_t *) 16; e.kc = (void *) 16; e.vc = (void *) 16;
+    e.Hkv = n_head_kv; e.dh = head_dim; e.n_ctx = 8; e.n_rot = n_rot; e.neox = rope_neox ? 1 : 0;
     f.epi = &e;
-    const int rc = pm_gemv_fused_check(f);
-    return rc == -5 ? PM355_E_UNSUPPORTED : gemv_rc(rc);
+    pm_gemv_plan pl; return gemv_rc(pm_gemv_fused_plan(f, 0, pl), MV_QKV_CHECK);
+}
+int pm355_mul_mat_vec_fused_plan(const pm355_matvec_job * jobs, int njobs, int64_t K, int x_mode, const pm355_qkv_store * qkv, int n_cus, int32_t * out, int n_out) {
+    if (njobs < 1 || njobs > 3 || !jobs || x_mode < 0 || x_mode > 15 || !out) return -9;
+    const float * const dx = (const float *) 16;             // stands for an activation, a weight vector, partial sums: never followed
+    const int xm = x_mode & 3;
+    pm_gemv_fused f = fused_of(jobs, njobs, K, xm ? dx : nullptr, xm >= 2 ? dx : nullptr, 0.0f);
+    if (xm == 0) f.xq = dx;
+    if (xm == 3) { f.ss_in = (const double *) dx; f.n_ss = 1; }
+    if (x_mode & 4) f.dbg_int = (int32_t *) dx;
+    if (x_mode & 8) f.ss_out = (double *) dx;
+    pm_qkv_epi e = {}; if (qkv) { e = qkv_epi_of(*qkv); f.epi = &e; }
+    pm_gemv_plan pl;
+    if (const int rc = pm_gemv_fused_plan(f, n_cus, pl)) return rc;
+    const pmv::GemvJob * j = pl.p.job;
+    const int32_t v[19] = {pl.grid, (int32_t) pl.lds, pl.ta, pl.tb, pl.pair, pl.first, j[0].split, j[1].split, j[2].split, j[0].nx_s, j[1].nx_s, j[2].nx_s,
+                           pl.form.pair, pl.form.dbg, pl.form.epi, pl.form.npre, pl.form.feat, pl.form.xm, pl.form.hot};
+    for (int i = 0; i < n_out && i < 19; ++i) out[i] = v[i];
+    return 0;
 }
 int pm355_mul_mat_vec_qkv_check(const pm355_matvec_job * jobs, int64_t K, int n_head_kv, int head_dim, int n_rot) {
     return pm355_mul_mat_vec_qkv_check_ex(jobs, K, n_head_kv, head_dim, n_rot, 0);

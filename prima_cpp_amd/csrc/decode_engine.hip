@@ -585,9 +585,9 @@ int pm_eng_plan_phases(const pm_eng_plan * p) { return p ? (int) p->ph.size() : 
 int pm_eng_plan_add_matvec(pm_eng_plan * pl, const pm_gemv_fused & f) {
     if (!pl || pl->finished) return -1;
     EngPhase e = {};
-    int ta, tb, grid; bool pair; size_t lds;
-    const int rc = gemv_fill(f, 0, e.g, ta, tb, pair, lds, grid);
-    if (rc) return rc < 0 ? rc : -rc;
+    pm_gemv_plan pl_f; const int rc = pm_gemv_fused_plan(f, 0, pl_f);
+    if (rc) return rc;
+    e.g = pl_f.p; const int ta = pl_f.ta, tb = pl_f.tb, grid = pl_f.grid; const bool pair = pl_f.pair;
     // the row loops compiled into the engine kernel (phase_rows<>): wq | wk | wv with the rope / KV-store epilogue in the type mixtures of the Q4_K_M and
     // Q6_K files, single Q4_K / Q6_K matrices (wo, ffn_down), Q4_K / Q6_K pairs (ffn_gate | ffn_up). (Q8_0 weights take Q8_0 activations: not yet)
     // (all-Q6_K wq | wk | wv and Q6_K pairs - the Q6_K file type - are written (-DENG_ALL_TYPES) but not compiled in: eight instantiations of the phase body
@@ -598,7 +598,7 @@ int pm_eng_plan_add_matvec(pm_eng_plan * pl, const pm_gemv_fused & f) {
     if (f.dbg_int) return -11;
     const int nblk = f.K / 256;
     if (f.K % 256 || nblk > (e.g.xmode == 3 ? 4 * ENG_NW : 8 * ENG_NW)) return -12;
-    if ((size_t) ((f.K + 15) & ~15) + (size_t) (f.K / 16) * 4 + (size_t) ((nblk + 3) & ~3) * 4 + 256 + (size_t) ENG_NW * 2304 > (size_t) ENG_OUT_OFF) return -12;
+    if (pm_gemv_act_lds(f.K, 256) + 256 + (size_t) ENG_NW * 2304 > (size_t) ENG_OUT_OFF) return -12;
     if (pl->grid && pl->grid != grid) return -13;
     if (grid > ENG_MAXG) return -13;
     pl->grid = grid;

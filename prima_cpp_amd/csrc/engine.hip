@@ -337,35 +337,37 @@ int matmul_small(pm355_model * m, const Tensor & w, ActQ & a, int T, float * y, 
     return gemv(w, nullptr, a, T, y, bias, resid, st);
 }
 
-// single-token fused GEMV launch helper: jobs share the f32 activation `xf` (rms_norm'ed with norm_w when given)
-// ss_out: this launch leaves its per-workgroup sum-of-squares partials there and *n_ss_out receives their number (0: not served - the consumer
-// then reduces the row itself); ss_in / n_ss_in: partials of xf's sum of squares left by the producing launch
-int gemv_f32(pm355_model * m, const Tensor * const * ws, const Tensor * const * w2s, float * const * ys,
-             const float * const * biases, const float * const * resids, int nj,
-             const float * xf, const float * norm_w, hipStream_t st, const pm_qkv_epi * epi = nullptr,
-             double * ss_out = nullptr, int * n_ss_out = nullptr, const double * ss_in = nullptr, int n_ss_in = 0) {
+// single-token fused mat-vec: 1..3 jobs that share the f32 row `xf` (rms_norm'ed with norm_w when given)
+pm_gemv_job gemv_job(const Tensor & w, const Tensor * w2, float * y, const float * bias, const float * resid) {
+    return {w.type, (int) w.N, w.d, w2 ? w2->d : nullptr, y, bias, resid};
+}
+pm_gemv_fused gemv_over(const pm355_model * m, const float * xf, const float * norm_w, int64_t K, pm_gemv_job job0) {
     pm_gemv_fused f = {};
-    f.K = (int) ws[0]->K; f.njobs = nj; f.xf = xf; f.norm_w = norm_w; f.eps = m->hp.rms_eps; f.epi = epi;
-    for (int j = 0; j < nj; ++j) {
-        f.job[j].type = ws[j]->type; f.job[j].N = (int) ws[j]->N; f.job[j].W = ws[j]->d; f.job[j].W2 = w2s ? (w2s[j] ? w2s[j]->d : nullptr) : nullptr;
-        f.job[j].y = ys[j]; f.job[j].bias = biases ? biases[j] : nullptr; f.job[j].resid = resids ? resids[j] : nullptr;
-    }
-    if (n_ss_out) *n_ss_out = 0;
-    if (ss_out && n_ss_out) {
-        const int g = pm_gemv_fused_grid(f);
-        if (g > 0 && g <= 256) { f.ss_out = ss_out; *n_ss_out = g; }
-    }
-    if (ss_in && n_ss_in > 0 && norm_w) { f.ss_in = ss_in; f.n_ss = n_ss_in; }
+    f.K = (int) K; f.njobs = 1; f.xf = xf; f.norm_w = norm_w; f.eps = m->hp.rms_eps; f.job[0] = job0;
+    return f;
+}
+// RoPE + KV store into layer L's caches in the epilogue of its wq | wk | wv launch (mat-vec and small-batch mat-mul): position-pointer mode, transposed V cache
+pm_qkv_epi qkv_epi_of(const pm355_model * m, const Layer & L, long seq_stride) {
+    pm_qkv_epi e = {};
+    e.tab = m->rope_tab; e.pos = m->d_pos; e.seq = m->d_ctl; e.seq_stride = seq_stride; e.kc = L.kc; e.vc = L.vc;
+    e.Hkv = m->hp.n_head_kv; e.dh = m->hp.head_dim; e.n_ctx = m->hp.n_ctx; e.n_rot = m->rope.n_dims; e.neox = (m->rope.mode & 2) ? 1 : 0;
+    return e;
+}
+// launches f. ss_in / n_ss_in: partials of xf's sum of squares left by the producing launch (none: the launch reduces the row itself); ss_out: this launch
+// leaves its per-workgroup partials there and *n_ss_out receives their number (0: not served - the consumer then reduces the row itself)
+int launch_gemv(pm_gemv_fused f, hipStream_t st, const double * ss_in = nullptr, int n_ss_in = 0, double * ss_out = nullptr, int * n_ss_out = nullptr) {
+    pm_gemv_plan pl; if (n_ss_out) *n_ss_out = 0;
+    if (ss_out && n_ss_out && pm_gemv_fused_plan(f, 0, pl) == 0 && pl.grid <= 256) { f.ss_out = ss_out; *n_ss_out = pl.grid; }      // (ss_out changes the kernel form: planned again)
+    if (ss_in && n_ss_in > 0 && f.norm_w) { f.ss_in = ss_in; f.n_ss = n_ss_in; }
     return pm_launch_gemv_fused(f, st);
 }
 
 // result_norm + lm_head (+ greedy argmax) on ONE hidden row (build_llama's last sub-graph, src/llama.cpp:11191-11215)
 int run_head(pm355_model * m, const float * x_row, float * d_logits, int32_t * d_argmax, hipStream_t st, const double * ss_in = nullptr, int n_ss_in = 0) {
     if (!m->output.d || !m->out_norm.d) return seterr(m, PM355_E_UNSUPPORTED, "head: output / output_norm missing");
-    const Tensor * ow[1] = {&m->output};
     float * lg = d_logits ? d_logits : m->logits;
-    float * y[1] = {lg};
-    if (gemv_f32(m, ow, nullptr, y, nullptr, nullptr, 1, x_row, (const float *) m->out_norm.d, st, nullptr, nullptr, nullptr, ss_in, n_ss_in))
+    pm_gemv_fused f = gemv_over(m, x_row, (const float *) m->out_norm.d, m->output.K, gemv_job(m->output, nullptr, lg, nullptr, nullptr));
+    if (launch_gemv(f, st, ss_in, n_ss_in))
         return seterr(m, PM355_E_UNSUPPORTED, "head: fused lm_head gemv");
     if (d_argmax) pm_launch_argmax(lg, m->hp.n_vocab, d_argmax, nullptr, st);
     return 0;
@@ -410,9 +412,7 @@ pm355_model::EnginePlan * engine_plan_for(pm355_model * m, const float * cur, fl
     const int max_keys = head_score_keys(m) ? head_score_keys(m) : hp.n_ctx;
     double * ss_in0 = (double *) ((char *) act + per_bytes * (size_t) nl);
     const double * ss_prev = ss_in0; int n_prev = 1;          // partials of the sum of squares of `cur`
-    auto job = [](pm_gemv_fused & f, int j, const Tensor & w, const Tensor * w2, float * y, const float * bias, const float * resid) {
-        f.job[j].type = w.type; f.job[j].N = (int) w.N; f.job[j].W = w.d; f.job[j].W2 = w2 ? w2->d : nullptr; f.job[j].y = y; f.job[j].bias = bias; f.job[j].resid = resid;
-    };
+    pm_gemv_plan pp;
     for (int il = m->lo; il < m->hi; ++il) {
         Layer & L = m->layers[il - m->lo];
         char * base = (char *) act + per_bytes * (size_t) (il - m->lo);
@@ -422,39 +422,29 @@ pm355_model::EnginePlan * engine_plan_for(pm355_model * m, const float * cur, fl
         const long kvs = m->n_seq > 1 ? (long) hp.n_ctx * Hkv * dh : 0;
         int rc, n_wo, n_dn;
         {   // wq | wk | wv + rope + KV store
-            pm_gemv_fused f = {};
-            f.K = hp.n_embd; f.njobs = 3; f.xf = cur; f.norm_w = (const float *) L.t[PM355_T_ATTN_NORM].d; f.eps = hp.rms_eps;
-            job(f, 0, L.t[PM355_T_WQ], nullptr, q, (const float *) L.t[PM355_T_BQ].d, nullptr);
-            job(f, 1, L.t[PM355_T_WK], nullptr, m->k, (const float *) L.t[PM355_T_BK].d, nullptr);
-            job(f, 2, L.t[PM355_T_WV], nullptr, m->v, (const float *) L.t[PM355_T_BV].d, nullptr);
-            const pm_qkv_epi qe = {m->rope_tab, m->d_pos, m->d_ctl, nullptr, kvs, L.kc, L.vc, Hkv, dh, hp.n_ctx, m->rope.n_dims, 0, (m->rope.mode & 2) ? 1 : 0};
+            pm_gemv_fused f = gemv_over(m, cur, (const float *) L.t[PM355_T_ATTN_NORM].d, hp.n_embd, gemv_job(L.t[PM355_T_WQ], nullptr, q, (const float *) L.t[PM355_T_BQ].d, nullptr));
+            f.njobs = 3; f.job[1] = gemv_job(L.t[PM355_T_WK], nullptr, m->k, (const float *) L.t[PM355_T_BK].d, nullptr);
+            f.job[2] = gemv_job(L.t[PM355_T_WV], nullptr, m->v, (const float *) L.t[PM355_T_BV].d, nullptr);
+            const pm_qkv_epi qe = qkv_epi_of(m, L, kvs);
             f.epi = &qe; f.ss_in = ss_prev; f.n_ss = n_prev;
             if ((rc = pm_eng_plan_add_matvec(pl, f))) return refuse("wq | wk | wv", rc);
         }
         if ((rc = pm_eng_plan_add_attention(pl, q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, att, H, Hkv, dh, hp.n_ctx, kq_scale, max_keys))) return refuse("attention", rc);
         {   // wo + residual, leaves the partials of ffn_norm
-            pm_gemv_fused f = {};
-            f.K = (int) L.t[PM355_T_WO].K; f.njobs = 1; f.xf = att; f.eps = hp.rms_eps;
-            job(f, 0, L.t[PM355_T_WO], nullptr, x_mid, nullptr, cur);
-            n_wo = pm_gemv_fused_grid(f);
-            if (n_wo < 1 || n_wo > 256) return refuse("wo grid", n_wo);
+            pm_gemv_fused f = gemv_over(m, att, nullptr, L.t[PM355_T_WO].K, gemv_job(L.t[PM355_T_WO], nullptr, x_mid, nullptr, cur));
+            if ((rc = pm_gemv_fused_plan(f, 0, pp)) || (n_wo = pp.grid) > 256) return refuse("wo grid", rc ? rc : n_wo);
             f.ss_out = ss_wo;
             if ((rc = pm_eng_plan_add_matvec(pl, f))) return refuse("wo", rc);
         }
         if (L.t[PM355_T_FFN_GATE].type != L.t[PM355_T_FFN_UP].type) return refuse("ffn_gate / ffn_up types", -1);
         {   // ffn_gate | ffn_up + silu * mul
-            pm_gemv_fused f = {};
-            f.K = hp.n_embd; f.njobs = 1; f.xf = x_mid; f.norm_w = (const float *) L.t[PM355_T_FFN_NORM].d; f.eps = hp.rms_eps;
-            job(f, 0, L.t[PM355_T_FFN_GATE], &L.t[PM355_T_FFN_UP], hbuf, nullptr, nullptr);
+            pm_gemv_fused f = gemv_over(m, x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, hp.n_embd, gemv_job(L.t[PM355_T_FFN_GATE], &L.t[PM355_T_FFN_UP], hbuf, nullptr, nullptr));
             f.ss_in = ss_wo; f.n_ss = n_wo;
             if ((rc = pm_eng_plan_add_matvec(pl, f))) return refuse("ffn_gate | ffn_up", rc);
         }
         {   // ffn_down + residual, leaves the partials of the next attn_norm / output_norm
-            pm_gemv_fused f = {};
-            f.K = (int) L.t[PM355_T_FFN_DOWN].K; f.njobs = 1; f.xf = hbuf; f.eps = hp.rms_eps;
-            job(f, 0, L.t[PM355_T_FFN_DOWN], nullptr, x_next, nullptr, x_mid);
-            n_dn = pm_gemv_fused_grid(f);
-            if (n_dn < 1 || n_dn > 256) return refuse("ffn_down grid", n_dn);
+            pm_gemv_fused f = gemv_over(m, hbuf, nullptr, L.t[PM355_T_FFN_DOWN].K, gemv_job(L.t[PM355_T_FFN_DOWN], nullptr, x_next, nullptr, x_mid));
+            if ((rc = pm_gemv_fused_plan(f, 0, pp)) || (n_dn = pp.grid) > 256) return refuse("ffn_down grid", rc ? rc : n_dn);
             f.ss_out = ss_dn;
             if ((rc = pm_eng_plan_add_matvec(pl, f))) return refuse("ffn_down", rc);
         }
@@ -513,17 +503,17 @@ int run_layers_fused(pm355_model * m, const float * cur, float * d_x_out, const 
         float * x_mid = (cur == bufs[0]) ? bufs[1] : bufs[0];
         float * x_nxt = (x_mid == bufs[0]) ? bufs[1] : bufs[0];
         {
-            const Tensor * ws[3] = {&L.t[PM355_T_WQ], &L.t[PM355_T_WK], &L.t[PM355_T_WV]};
-            float * ys[3] = {q, k, v};
-            const float * bs[3] = {(const float *) L.t[PM355_T_BQ].d, (const float *) L.t[PM355_T_BK].d, (const float *) L.t[PM355_T_BV].d};
-            const float * nw = (const float *) L.t[PM355_T_ATTN_NORM].d;
-            const long kvs_e = m->n_seq > 1 ? (long) hp.n_ctx * Hkv * dh : 0;
-            pm_qkv_epi qe = {m->rope_tab, m->d_pos, m->d_ctl, nullptr, kvs_e, L.kc, L.vc, Hkv, dh, hp.n_ctx, m->rope.n_dims, 0, (m->rope.mode & 2) ? 1 : 0};
+            // wq | wk | wv: with the attention in the tail, else with the RoPE + KV-store epilogue, else as three plain jobs, else one launch per matrix
+            const int kinds[3] = {PM355_T_WQ, PM355_T_WK, PM355_T_WV};
+            pm_gemv_fused f = gemv_over(m, cur, (const float *) L.t[PM355_T_ATTN_NORM].d, L.t[PM355_T_WQ].K, gemv_job(L.t[PM355_T_WQ], nullptr, q, (const float *) L.t[PM355_T_BQ].d, nullptr));
+            f.njobs = 3; f.job[1] = gemv_job(L.t[PM355_T_WK], nullptr, k, (const float *) L.t[PM355_T_BK].d, nullptr);
+            f.job[2] = gemv_job(L.t[PM355_T_WV], nullptr, v, (const float *) L.t[PM355_T_BV].d, nullptr);
+            pm_qkv_epi qe = qkv_epi_of(m, L, m->n_seq > 1 ? (long) hp.n_ctx * Hkv * dh : 0); f.epi = &qe;
             bool qkv_done = false;
             if (tail) {
                 qe.att_out = att; qe.att_ticket = m->att_tk; qe.att_err = (int *) (m->att_tk + 64); qe.kq_scale = kq_scale; qe.n_head = H;
                 qe.att_max_keys = head_score_keys(m);
-                qkv_done = gemv_f32(m, ws, nullptr, ys, bs, nullptr, 3, cur, nw, st, &qe, nullptr, nullptr, ss_dn, n_dn) == 0;
+                qkv_done = launch_gemv(f, st, ss_dn, n_dn) == 0;
                 if (!qkv_done) {
                     if (il != m->lo) return seterr(m, PM355_E_UNSUPPORTED, "decode: attention tail served for some layers only");
                     tail = false; m->attn_tail = false;    // (grid does not split into power-of-two runs per KV head, head_dim: the separate launch)
@@ -531,15 +521,19 @@ int run_layers_fused(pm355_model * m, const float * cur, float * d_x_out, const 
                 }
             }
             if (epi && !qkv_done) {
-                qkv_done = gemv_f32(m, ws, nullptr, ys, bs, nullptr, 3, cur, nw, st, &qe, nullptr, nullptr, ss_dn, n_dn) == 0;
+                qkv_done = launch_gemv(f, st, ss_dn, n_dn) == 0;
                 if (!qkv_done) {
                     if (il != m->lo) return seterr(m, PM355_E_UNSUPPORTED, "decode: QKV epilogue served for some layers only");
                     epi = false;                       // (shape / type mix without the epilogue kernel: the whole window takes the round-2 form)
                 }
             }
-            if (!qkv_done && gemv_f32(m, ws, nullptr, ys, bs, nullptr, 3, cur, nw, st, nullptr, nullptr, nullptr, ss_dn, n_dn)) {
-                for (int j = 0; j < 3; ++j)               // type mix without a 3-job kernel: one launch per matrix
-                    if (gemv_f32(m, ws + j, nullptr, ys + j, bs + j, nullptr, 1, cur, nw, st)) return seterr(m, PM355_E_UNSUPPORTED, "decode: fused qkv gemv");
+            f.epi = nullptr;
+            if (!qkv_done && launch_gemv(f, st, ss_dn, n_dn)) {
+                f.njobs = 1;
+                for (int j = 0; j < 3; ++j) {             // type mix without a 3-job kernel: one launch per matrix (each reduces the row itself)
+                    f.job[0] = f.job[j]; f.K = (int) L.t[kinds[j]].K;
+                    if (launch_gemv(f, st)) return seterr(m, PM355_E_UNSUPPORTED, "decode: fused qkv gemv");
+                }
             }
         }
         if (il == m->lo) {                             // the first layer's wq | wk | wv launch has settled epi and tail
@@ -566,20 +560,20 @@ int run_layers_fused(pm355_model * m, const float * cur, float * d_x_out, const 
         }
         if (rc) return seterr(m, PM355_E_RANGE, why);
         {
-            const Tensor * w[1] = {&L.t[PM355_T_WO]}; float * y[1] = {x_mid}; const float * r[1] = {cur};
-            if (gemv_f32(m, w, nullptr, y, nullptr, r, 1, att, nullptr, st, nullptr, ss_wo, &n_wo)) return seterr(m, PM355_E_UNSUPPORTED, "decode: fused wo gemv");
+            pm_gemv_fused f = gemv_over(m, att, nullptr, L.t[PM355_T_WO].K, gemv_job(L.t[PM355_T_WO], nullptr, x_mid, nullptr, cur));
+            if (launch_gemv(f, st, nullptr, 0, ss_wo, &n_wo)) return seterr(m, PM355_E_UNSUPPORTED, "decode: fused wo gemv");
         }
         if (L.t[PM355_T_FFN_GATE].type != L.t[PM355_T_FFN_UP].type)
             return seterr(m, PM355_E_UNSUPPORTED, "decode: ffn_gate and ffn_up of different types");
         {
-            const Tensor * w[1] = {&L.t[PM355_T_FFN_GATE]}; const Tensor * w2[1] = {&L.t[PM355_T_FFN_UP]}; float * y[1] = {hbuf};
-            if (gemv_f32(m, w, w2, y, nullptr, nullptr, 1, x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, st, nullptr, nullptr, nullptr, ss_wo, n_wo))
+            pm_gemv_fused f = gemv_over(m, x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, L.t[PM355_T_FFN_GATE].K, gemv_job(L.t[PM355_T_FFN_GATE], &L.t[PM355_T_FFN_UP], hbuf, nullptr, nullptr));
+            if (launch_gemv(f, st, ss_wo, n_wo))
                 return seterr(m, PM355_E_UNSUPPORTED, "decode: fused gate/up gemv");
         }
         float * x_next = (il == m->hi - 1 && d_x_out) ? d_x_out : x_nxt;
         {
-            const Tensor * w[1] = {&L.t[PM355_T_FFN_DOWN]}; float * y[1] = {x_next}; const float * r[1] = {x_mid};
-            if (gemv_f32(m, w, nullptr, y, nullptr, r, 1, hbuf, nullptr, st, nullptr, ss_dn, &n_dn)) return seterr(m, PM355_E_UNSUPPORTED, "decode: fused down gemv");
+            pm_gemv_fused f = gemv_over(m, hbuf, nullptr, L.t[PM355_T_FFN_DOWN].K, gemv_job(L.t[PM355_T_FFN_DOWN], nullptr, x_next, nullptr, x_mid));
+            if (launch_gemv(f, st, nullptr, 0, ss_dn, &n_dn)) return seterr(m, PM355_E_UNSUPPORTED, "decode: fused down gemv");
         }
         layer_release(m, il, st);
         cur = x_next;
@@ -704,8 +698,7 @@ int small_qkv(pm355_model * m, const Layer & L, ActQ a, int T, bool small, bool 
     const Tensor & wq = L.t[PM355_T_WQ], & wk = L.t[PM355_T_WK], & wv = L.t[PM355_T_WV];
     const pm_mmq_job jobs[3] = {mmq_job(wq, m->q, (const float *) L.t[PM355_T_BQ].d, nullptr), mmq_job(wk, m->k, (const float *) L.t[PM355_T_BK].d, nullptr),
                                 mmq_job(wv, m->v, (const float *) L.t[PM355_T_BV].d, nullptr)};
-    const pm_qkv_epi qe = {m->rope_tab, m->d_pos, m->d_ctl, nullptr, (long) hp.n_ctx * hp.n_head_kv * hp.head_dim, L.kc, L.vc, hp.n_head_kv, hp.head_dim,
-                           hp.n_ctx, m->rope.n_dims, 0, 0};
+    const pm_qkv_epi qe = qkv_epi_of(m, L, (long) hp.n_ctx * hp.n_head_kv * hp.head_dim);
     auto fused = [&](int n, const pm_qkv_epi * e) { return pm_launch_mmq_i8(jobs, n, {a.k, nullptr, a.tab}, (int) wq.K, T, e, st) == 0; };
     if (small && wq.type == wk.type && wk.K == wq.K && wv.K == wq.K) {      // (one K per launch: a job carries none)
         if (small_rope_epi(m, T) && fused(3, &qe)) { rope_done = true; return 0; }

@@ -33,7 +33,7 @@ using namespace pmv;
 constexpr uint32_t GEMV_TYPES = PM_QUANT_WEIGHTS;
 // the instantiated (TA, TB) pairs of the fused launch, TA = the type of job 0 (the kernel pre-issues it): one type, or the Q4_K_M mixtures of wq | wk | wv
 // (attn_v is Q6_K / Q5_K next to Q4_K). Q8_0 / Q5_0 jobs need Q8_0-quantized activations, the K-quants Q8_K, and one prologue serves one family:
-// no pair across the two, and Q5_0 next to Q8_0 in one launch is not instantiated. gemv_fill validates against this list, pm_launch_gemv_fused dispatches over it.
+// no pair across the two, and Q5_0 next to Q8_0 in one launch is not instantiated. pm_gemv_fused_plan validates against this list, gemv_kernel_of dispatches over it.
 #define PM_GEMV_TYPE_PAIRS(X) X(PM_Q4_K, PM_Q4_K) X(PM_Q5_K, PM_Q5_K) X(PM_Q6_K, PM_Q6_K) X(PM_Q8_0, PM_Q8_0) X(PM_Q5_0, PM_Q5_0) X(PM_Q4_K, PM_Q6_K) X(PM_Q4_K, PM_Q5_K)
 
 // (what the type table says about the mat-vec is what the kernels are compiled with; every type is the TA of some pair)
@@ -51,7 +51,7 @@ namespace {
 // keeps one mode's code instead of four behind scalar branches
 // HOT: everything else the decode launches of the Llama-family layer never use is pinned too (no bias, one job outside wq | wk | wv, no residual on
 // the pair launch, transposed V cache and - HOT 1: the engine - position-pointer mode / HOT 2: the plug-in - ggml-graph mode in the QKV epilogue):
-// launch_types() checks that the argument block really looks like that
+// gemv_hot_of() checks that the argument block really looks like that
 template <int TA, int TB, bool PAIR, bool DBG, bool EPI = false, int NPRE = 2, int FEAT = 0, int XM = -1, int HOT = 0>
 #ifdef PM_NO_PRELOAD_ARGS
 __global__ __launch_bounds__(PM_GEMV_BLOCK, 4) void gemv_q_kernel(GemvP p) {
@@ -82,86 +82,99 @@ __global__ __launch_bounds__(PM_GEMV_BLOCK, 4) void gemv_q_kernel(const float * 
     // (Q5_K: two 32-weight units per lane and step = 24-VGPR sets with the high-bit plane; a second pre-issued set spills)
     gemv_body<TA, TB, PAIR, DBG, 1, EPI, (TA == PM_Q5_K && NPRE == 2) ? 1 : NPRE, FEAT>(p, smem, nred);
 }
-template <int TA, int TB>
-int launch_types(const GemvP & p_in, bool pair, int grid, size_t lds, bool dbg, hipStream_t st, bool epi = false) {
-    const GemvP & p = p_in;
-    auto go = [&](auto kern) {
-        pm_allow_big_lds((const void *) kern, lds);
-#ifdef PM_NO_PRELOAD_ARGS
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(PM_GEMV_BLOCK), lds, st, p);
-#else
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(PM_GEMV_BLOCK), lds, st, p.xf, p.norm_w, p.job[0].W, p.job[0].W2, p.job[0].row_stride, p.K, p.xmode, p.job[0].N, p.job[0].U, p);
-#endif
-    };
-    const bool ss = p.ss_out != nullptr || p.xmode == 3;          // producer or consumer of per-workgroup partial sums of squares
-#if !PM_EXPERIMENTS
-    if (ss || (epi && p.epi.att_out != nullptr)) return -8;         // (sum-of-squares partials / attention tail: experiments library only)
-#endif
-    static const bool xm_spec = [] { const char * e = getenv("PM355_XMODE_SPEC"); return !(e && e[0] == '0'); }();     // (A/B switches)
-    static const bool hot_spec = xm_spec && [] { const char * e = getenv("PM355_HOT_SPEC"); return !(e && e[0] == '0'); }();
-    const bool one_job = p.job[1].N == 0 && p.job[2].N == 0;
-    const bool tail = epi && p.epi.att_out != nullptr; (void) tail;
-    const bool neox = epi && (p.job[0].nx_s > 0 || p.job[1].nx_s > 0 || p.job[2].nx_s > 0);
-    if (pair) {
-        if (TA != TB) return -1;
-        // (pair launches: one step of pre-issue - two sets of two matrices next to the activation registers spill)
-        if (dbg) { if (ss) return -6; go(gemv_q_kernel<TA, TA, true, true, false, 1>); }
-#if PM_EXPERIMENTS
-        else if (ss) go(gemv_q_kernel<TA, TA, true, false, false, 1, PM_FEAT_SS>);
-#endif
-        else if (p.xmode == 2 && hot_spec && one_job && !p.job[0].bias && !p.job[0].resid && !p.job[0].split) go(gemv_q_kernel<TA, TA, true, false, false, 1, 0, 2, 1>);
-        else if (p.xmode == 2 && xm_spec) go(gemv_q_kernel<TA, TA, true, false, false, 1, 0, 2>);
-        else go(gemv_q_kernel<TA, TA, true, false, false, 1>);
-    } else if (epi) {
-        if (dbg) return -1;
-#if PM_EXPERIMENTS
-        if (tail) {
-            // the tail is compiled for the wq | wk | wv type mixtures of the Q4_K_M files only (wq Q4_K; wv Q4_K / Q5_K / Q6_K)
-            if constexpr (TA == PM_Q4_K) { if (ss) go(gemv_q_kernel<TA, TB, false, false, true, 2, PM_FEAT_SS | PM_FEAT_TAIL>); else go(gemv_q_kernel<TA, TB, false, false, true, 2, PM_FEAT_TAIL>); }
-            else return -7;
-        } else if (neox && ss) go(gemv_q_kernel<TA, TB, false, false, true, 2, PM_FEAT_NEOX | PM_FEAT_SS>);
-        else if (ss) go(gemv_q_kernel<TA, TB, false, false, true, 2, PM_FEAT_SS>);
-        else
-#endif
-        if (neox) go(gemv_q_kernel<TA, TB, false, false, true, 2, PM_FEAT_NEOX>);
-        else if (p.xmode == 2 && hot_spec && !p.job[0].bias && !p.job[1].bias && !p.job[2].bias && !p.epi.v_rowmajor &&
-                 p.job[0].role == 1 && p.job[1].role == 2 && p.job[2].role == 3 && !p.job[0].is_b && !p.job[1].is_b && p.job[2].is_b == (TA != TB ? 1 : 0) &&
-                 !p.job[0].split && !p.job[0].resid && !p.job[1].resid && !p.job[2].resid) { if (p.epi.dyn) go(gemv_q_kernel<TA, TB, false, false, true, 2, 0, 2, 2>); else go(gemv_q_kernel<TA, TB, false, false, true, 2, 0, 2, 1>); }
-        else if (p.xmode == 2 && xm_spec) go(gemv_q_kernel<TA, TB, false, false, true, 2, 0, 2>);
-        else go(gemv_q_kernel<TA, TB, false, false, true>);
-    } else {
-        if (dbg) { if (ss) return -6; go(gemv_q_kernel<TA, TB, false, true, false, 1>); }     // (test hook: one pre-issued step - with two, the Q6_K form sat on the 128-VGPR cliff with a spilled register)
-#if PM_EXPERIMENTS
-        else if (ss) go(gemv_q_kernel<TA, TB, false, false, false, 2, PM_FEAT_SS>);
-#endif
-        else if (p.xmode == 1 && hot_spec && one_job && !p.job[0].bias && p.job[0].resid && !p.job[0].split && !p.job[0].is_b) go(gemv_q_kernel<TA, TB, false, false, false, 2, 0, 1, 1>);
-        else if (p.xmode == 1 && xm_spec) go(gemv_q_kernel<TA, TB, false, false, false, 2, 0, 1>);
-        else if (p.xmode == 2 && xm_spec) go(gemv_q_kernel<TA, TB, false, false, false, 2, 0, 2>);
-        else go(gemv_q_kernel<TA, TB, false, false>);
-    }
-    return 0;
+// The forms gemv_q_kernel is instantiated in, X(PAIR, DBG, EPI, NPRE, FEAT, XM, HOT), in the launcher's order of preference: gemv_form_of() takes the first row
+// the argument block meets. A row requires the launch to be (not) a pair / debug / epilogue launch, to use exactly the features FEAT (gemv_feat_of), to have
+// xmode == XM where XM >= 0 (and PM355_XMODE_SPEC not 0), and for HOT to hold already every value the kernel pins (gemv_hot_of; and PM355_HOT_SPEC not 0).
+// NPRE asks nothing: 1 pre-issued step where two spill (pair launches: two sets of two matrices; the debug hook: Q6_K sat on the 128-VGPR cliff). Compiled
+// (gemv_form_kernel) per pair of PM_GEMV_TYPE_PAIRS; PAIR rows for TA == TB only, TAIL rows for TA == Q4_K only (the Q4_K_M mixtures), SS / TAIL rows in the
+// experiments library only - the product library answers -8 for what they serve.
+#define PM_GEMV_FORMS(X) \
+    X(true,  true,  false, 1, 0, -1, 0)            /* ffn_gate | ffn_up */ \
+    X(true,  false, false, 1, PM_FEAT_SS, -1, 0) \
+    X(true,  false, false, 1, 0, 2, 1) \
+    X(true,  false, false, 1, 0, 2, 0) \
+    X(true,  false, false, 1, 0, -1, 0) \
+    X(false, false, true,  2, PM_FEAT_SS | PM_FEAT_TAIL, -1, 0)       /* wq | wk | wv with the RoPE + KV-store epilogue */ \
+    X(false, false, true,  2, PM_FEAT_TAIL, -1, 0) \
+    X(false, false, true,  2, PM_FEAT_NEOX | PM_FEAT_SS, -1, 0) \
+    X(false, false, true,  2, PM_FEAT_SS, -1, 0) \
+    X(false, false, true,  2, PM_FEAT_NEOX, -1, 0) \
+    X(false, false, true,  2, 0, 2, 2) \
+    X(false, false, true,  2, 0, 2, 1) \
+    X(false, false, true,  2, 0, 2, 0) \
+    X(false, false, true,  2, 0, -1, 0) \
+    X(false, true,  false, 1, 0, -1, 0)            /* one to three plain jobs: wo, ffn_down, lm_head; wq | wk | wv without the epilogue */ \
+    X(false, false, false, 2, PM_FEAT_SS, -1, 0) \
+    X(false, false, false, 2, 0, 1, 1) \
+    X(false, false, false, 2, 0, 1, 0) \
+    X(false, false, false, 2, 0, 2, 0) \
+    X(false, false, false, 2, 0, -1, 0)
+#define PM_F(...) {__VA_ARGS__},
+constexpr pm_gemv_form GEMV_FORMS[] = { PM_GEMV_FORMS(PM_F) };
+#undef PM_F
+constexpr int N_GEMV_FORMS = (int) (sizeof(GEMV_FORMS) / sizeof(GEMV_FORMS[0])), PM_FEAT_EXP = PM_FEAT_SS | PM_FEAT_TAIL;
+typedef decltype(&gemv_q_kernel<PM_Q4_K, PM_Q4_K, false, false>) GemvKernel;
+template <int TA, int TB, bool PAIR, bool DBG, bool EPI, int NPRE, int FEAT, int XM, int HOT>
+GemvKernel gemv_form_kernel() {
+    if constexpr ((PAIR && TA != TB) || ((FEAT & PM_FEAT_TAIL) && TA != PM_Q4_K) || ((FEAT & PM_FEAT_EXP) && !PM_EXPERIMENTS)) return nullptr;
+    else return gemv_q_kernel<TA, TB, PAIR, DBG, EPI, NPRE, FEAT, XM, HOT>;
 }
-
-int nv_of(int type) { return pm_type_info(type).nv; }
-
+#define PM_K(...) gemv_form_kernel<TA, TB, __VA_ARGS__>(),
+template <int TA, int TB> GemvKernel gemv_kernel_row(int row) { static const GemvKernel t[] = { PM_GEMV_FORMS(PM_K) }; return t[row]; }
+#undef PM_K
+GemvKernel gemv_kernel_of(int ta, int tb, int row) {
+#define PM_L(TA_, TB_) if (ta == TA_ && tb == TB_) return gemv_kernel_row<TA_, TB_>(row);
+    PM_GEMV_TYPE_PAIRS(PM_L)
+#undef PM_L
+    return nullptr;
+}
 bool pair_instantiated(int ta, int tb) {
-#define PM_IS(TA_, TB_) if (ta == TA_ && tb == TB_) return true;
-    PM_GEMV_TYPE_PAIRS(PM_IS)
+#define PM_IS(TA_, TB_) || (ta == TA_ && tb == TB_)
+    return false PM_GEMV_TYPE_PAIRS(PM_IS);
 #undef PM_IS
-    return false;
+}
+// the FEAT a launch needs: producer or consumer of sum-of-squares partials, attention in the tail (its instantiations carry the NEOX row mapping), NEOX rope
+int gemv_feat_of(const GemvP & p, bool epi) {
+    const int ss = (p.ss_out != nullptr || p.xmode == 3) ? PM_FEAT_SS : 0;
+    if (epi && p.epi.att_out != nullptr) return ss | PM_FEAT_TAIL;
+    return ss | (epi && (p.job[0].nx_s > 0 || p.job[1].nx_s > 0 || p.job[2].nx_s > 0) ? PM_FEAT_NEOX : 0);
+}
+// the HOT a launch may take: 0, or the variant whose pinned values (gemv_q_kernel) the block holds anyway - else the kernel would drop a bias, a residual or a job
+int gemv_hot_of(const GemvP & p, bool mixed, bool pair, bool epi) {
+    const GemvJob * j = p.job;
+    if (j[0].bias || j[0].split) return 0;
+    // one job: ffn_gate | ffn_up without a residual; wo / ffn_down always with one
+    if (!epi) return j[1].N == 0 && j[2].N == 0 && (pair ? !j[0].resid : j[0].resid && !j[0].is_b) ? 1 : 0;
+    // wq, wk, wv in this order (no TA-first swap), wv alone of the second type, transposed V cache; 1: position pointer (the engine), 2: ggml-graph mode (the plug-in)
+    if (j[1].bias || j[2].bias || j[0].resid || j[1].resid || j[2].resid || p.epi.v_rowmajor) return 0;
+    if (j[0].role != 1 || j[1].role != 2 || j[2].role != 3 || j[0].is_b || j[1].is_b || j[2].is_b != (mixed ? 1 : 0)) return 0;
+    return p.epi.dyn ? 2 : 1;
+}
+// Which row of PM_GEMV_FORMS a filled argument block launches, or the refusal (pm355_kernels.h). Pure host logic: the only place the launcher's conditions live
+int gemv_form_of(const GemvP & p, int ta, int tb, bool pair, bool epi, bool dbg, bool xm_spec, bool hot_spec) {
+    const int feat = gemv_feat_of(p, epi), hot = hot_spec ? gemv_hot_of(p, ta != tb, pair, epi) : 0;
+    if (!PM_EXPERIMENTS && (feat & PM_FEAT_EXP)) return -8;
+    if ((pair && ta != tb) || (epi && dbg)) return -1;
+    if (dbg && (feat & PM_FEAT_SS)) return -6;
+    if ((feat & PM_FEAT_TAIL) && ta != PM_Q4_K) return -7;
+    for (int r = 0; r < N_GEMV_FORMS; ++r) {
+        const pm_gemv_form & f = GEMV_FORMS[r];
+        if (f.pair == pair && f.dbg == dbg && f.epi == epi && f.feat == feat && (f.xm < 0 || (xm_spec && p.xmode == f.xm)) && (!f.hot || f.hot == hot)) return r;
+    }
+    return -1;
 }
 
 } // namespace
 
 static int g_num_cus_dev[16] = {};
-static int num_cus() {
+int pm_device_cus() {
     const int dv = pm_cur_dev();
     if (!g_num_cus_dev[dv]) { hipDeviceProp_t pr; g_num_cus_dev[dv] = hipGetDeviceProperties(&pr, dv) == hipSuccess ? pr.multiProcessorCount : 256; }
     return g_num_cus_dev[dv];
 }
 
 // (a type the mat-vec does not serve answers K / 32 as it always did: the launch that follows refuses it)
-int pm_gemv_units_per_row(int type, int64_t K) { return (int) (K / (nv_of(type) ? nv_of(type) : 32)); }
+int pm_gemv_units_per_row(int type, int64_t K) { const int nv = pm_type_info(type).nv; return (int) (K / (nv ? nv : 32)); }
 
 size_t pm_weight_row_stride(int type, int64_t K) {
     if (!pm_type_info(type).pad) return pm_weight_row_bytes(type, K);
@@ -169,12 +182,11 @@ size_t pm_weight_row_stride(int type, int64_t K) {
     return type == PM_Q6_K ? pm_q6k_row_stride(nb) : type == PM_Q5_0 ? pm_q50_row_stride(nb) : pm_q80_row_stride(nb);
 }
 
-// Validates a fused job list and fills the kernel argument block. (ta, tb) are the (at most two) quant types in the order of one of the
-// instantiated kernels (PM_GEMV_TYPE_PAIRS); job 0 is always a `ta` job (the kernel pre-issues it). grid_fixed > 0: the caller's grid
-// (attn_wo.hip), else chosen here.
-int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_out, int & tb_out, bool & pair_out, size_t & lds_out, int & grid_out) {
-    if (a.njobs < 1 || a.njobs > 3) return -4;
-    p = GemvP{};
+// Validates a fused job list, fills the kernel argument block and chooses the grid, the LDS bytes and the kernel form. (ta, tb) are the (at most two) quant
+// types in the order of one of the instantiated kernels (PM_GEMV_TYPE_PAIRS); job 0 is always a `ta` job (the kernel pre-issues it).
+int pm_gemv_fused_plan(const pm_gemv_fused & a, int cus, pm_gemv_plan & out) {
+    if (a.njobs < 1 || a.njobs > 3) return -9;
+    GemvP & p = out.p = GemvP{};
     p.K = a.K; p.xq = (const uint8_t *) a.xq; p.xf = a.xf; p.norm_w = a.norm_w; p.eps = a.eps; p.dbg = a.dbg_int;
     p.xmode = a.xq ? 0 : (a.norm_w ? (a.ss_in ? 3 : 2) : 1);
     if (a.ss_in && (!a.norm_w || a.xq || a.n_ss < 1 || a.n_ss > 256)) return -6;
@@ -196,18 +208,17 @@ int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_
         if (!pair_instantiated(ta, tb)) return -1;
     }
     // one workgroup of 16 waves per CU; every workgroup takes an equal slice of the rows of EVERY job
-    int grid = grid_fixed > 0 ? grid_fixed : (1024 / PM_GEMV_BLOCK) * num_cus();
+    int grid = (1024 / PM_GEMV_BLOCK) * (cus > 0 ? cus : pm_device_cus());
     long tot_rows = 0;
     for (int j = 0; j < a.njobs; ++j) tot_rows += a.job[j].N;
-    int rows_cap = PM_MAX_ROWS_PER_WG;
-    if (grid_fixed > 0) rows_cap = (int) ((tot_rows + grid - 1) / grid + 3 > PM_MAX_ROWS_PER_WG ? (tot_rows + grid - 1) / grid + 4 : PM_MAX_ROWS_PER_WG);
-    else while ((tot_rows + grid - 1) / grid + 3 > PM_MAX_ROWS_PER_WG) grid *= 2;
+    while ((tot_rows + grid - 1) / grid + 3 > PM_MAX_ROWS_PER_WG) grid *= 2;
     for (int j = 0; j < 3; ++j) {
         GemvJob & g = p.job[j];
         if (j >= a.njobs) { g.N = 0; continue; }
         const pm_gemv_job & s = a.job[j];
+        const int nv = pm_type_info(s.type).nv;
         g.W = (const uint8_t *) s.W; g.W2 = (const uint8_t *) s.W2; g.y = s.y; g.bias = s.bias; g.resid = s.resid;
-        g.N = s.N; g.is_b = (s.type != ta); g.U = a.K / nv_of(s.type);
+        g.N = s.N; g.is_b = (s.type != ta); g.U = a.K / nv;
         g.row_stride = (long) pm_weight_row_stride(s.type, a.K);
         g.role = 0; g.split = 0;
         if (a.epi) {
@@ -215,7 +226,7 @@ int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_
             // workgroup fewer rows than it has waves is dealt out step by step (row, chunk) so that all 16 waves share its rows
             if (pair || a.njobs != 3 || s.N % (2 * grid) || a.dbg_int) return -5;
             g.role = j + 1;
-            const int upl = (g.U + 63) >> 6, ch = nv_of(s.type) == 64 ? PM_CH64 : PM_CH32, cpr = (upl + ch - 1) / ch;
+            const int upl = (g.U + 63) >> 6, ch = nv == 64 ? PM_CH64 : PM_CH32, cpr = (upl + ch - 1) / ch;
             g.split = (j > 0 && s.N / grid < PM_GEMV_NW && cpr > 1) ? 1 : 0;
             if (a.epi->neox && j < 2) {
                 // NEOX pairs (i, i + n_rot / 2): the slice of every workgroup = two runs of sl / 2 rows, n_rot / 2 apart, inside one head
@@ -232,7 +243,7 @@ int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_
     size_t att_lds = 0;
     if (a.epi) {
         const pm_qkv_epi & e = *a.epi;
-        if (grid_fixed > 0 || e.dh % 2 || e.n_rot % 2 || e.n_rot > e.dh || a.job[0].N % e.dh || a.job[1].N != e.Hkv * e.dh || a.job[2].N != e.Hkv * e.dh) return -5;
+        if (e.dh % 2 || e.n_rot % 2 || e.n_rot > e.dh || a.job[0].N % e.dh || a.job[1].N != e.Hkv * e.dh || a.job[2].N != e.Hkv * e.dh) return -5;
         // (ggml-graph mode has no position pointer: the scalar loads of the un-taken branch may still be issued - give them a valid address)
         p.epi = QkvEpi{e.tab, e.pos ? e.pos : e.dyn, e.seq, e.dyn, e.seq_stride, (uint16_t *) e.kc, (uint16_t *) e.vc, e.Hkv * e.dh, e.dh, e.n_ctx, e.n_rot, e.v_rowmajor, e.neox,
                        nullptr, nullptr, nullptr, nullptr, 0.0f, 0, 0};
@@ -247,39 +258,35 @@ int pmv::gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta_
             p.epi.att_H = e.n_head; p.epi.att_wgs = wgs;
         }
     }
+    out.first = 0;
     if (p.job[0].is_b)                                // the kernel pre-issues job 0 with the TA code path: put a TA job first
-        for (int j = 1; j < 3; ++j) if (p.job[j].N > 0 && !p.job[j].is_b) { const GemvJob t = p.job[0]; p.job[0] = p.job[j]; p.job[j] = t; break; }
-    const int ablk = pm_block_len(ta);
-    size_t lds = (size_t) ((a.K + 15) & ~15) + (size_t) (a.K / 16) * 4 + (size_t) ((a.K / ablk + 3) & ~3) * 4 + (size_t) rows_cap * 4;
+        for (int j = 1; j < 3; ++j) if (p.job[j].N > 0 && !p.job[j].is_b) { const GemvJob t = p.job[0]; p.job[0] = p.job[j]; p.job[j] = t; out.first = j; break; }
+    size_t lds = pm_gemv_act_lds(a.K, pm_block_len(ta)) + (size_t) PM_MAX_ROWS_PER_WG * 4;
     if (att_lds > lds) lds = att_lds;
     if (lds > 150 * 1024) return -4;
-    ta_out = ta; tb_out = tb; pair_out = pair; lds_out = lds; grid_out = grid;
+    static const bool xm_spec = [] { const char * e = getenv("PM355_XMODE_SPEC"); return !(e && e[0] == '0'); }();     // (A/B switches)
+    static const bool hot_spec = xm_spec && [] { const char * e = getenv("PM355_HOT_SPEC"); return !(e && e[0] == '0'); }();
+    if ((out.row = gemv_form_of(p, ta, tb, pair, a.epi != nullptr, a.dbg_int != nullptr, xm_spec, hot_spec)) < 0) return out.row;
+    out.ta = ta; out.tb = tb; out.pair = pair; out.grid = grid; out.lds = lds; out.form = GEMV_FORMS[out.row];
     return 0;
 }
 
-int pm_device_cus() { return num_cus(); }
-
-int pm_gemv_fused_check(const pm_gemv_fused & a) {
-    GemvP p; int ta, tb, grid; bool pair; size_t lds;
-    return gemv_fill(a, 0, p, ta, tb, pair, lds, grid);
-}
-
-int pm_gemv_fused_grid(const pm_gemv_fused & a) {
-    GemvP p; int ta, tb, grid; bool pair; size_t lds;
-    const int rc = gemv_fill(a, 0, p, ta, tb, pair, lds, grid);
-    return rc ? (rc < 0 ? rc : -rc) : grid;
+static int gemv_launch_plan(pm_gemv_plan & pl, hipStream_t st) {
+    const GemvKernel kern = gemv_kernel_of(pl.ta, pl.tb, pl.row); if (!kern) return -1;
+    GemvP & p = pl.p; p.ts = pm_ts_next_slot();
+    pm_allow_big_lds((const void *) kern, pl.lds);
+#ifdef PM_NO_PRELOAD_ARGS
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(PM_GEMV_BLOCK), pl.lds, st, p);
+#else
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(PM_GEMV_BLOCK), pl.lds, st, p.xf, p.norm_w, p.job[0].W, p.job[0].W2, p.job[0].row_stride, p.K, p.xmode, p.job[0].N, p.job[0].U, p);
+#endif
+    return 0;
 }
 
 // Fused launch: up to 3 matrices sharing one activation row.
 int pm_launch_gemv_fused(const pm_gemv_fused & a, hipStream_t st) {
-    GemvP p; int ta, tb, grid; bool pair; size_t lds;
-    const int rc = gemv_fill(a, 0, p, ta, tb, pair, lds, grid);
-    if (rc) return rc;
-    p.ts = pm_ts_next_slot();
-#define PM_L(TA_, TB_) if (ta == TA_ && tb == TB_) return launch_types<TA_, TB_>(p, pair, grid, lds, a.dbg_int != nullptr, st, a.epi != nullptr);
-    PM_GEMV_TYPE_PAIRS(PM_L)
-#undef PM_L
-    return -1;
+    pm_gemv_plan pl; const int rc = pm_gemv_fused_plan(a, 0, pl);
+    return rc ? rc : gemv_launch_plan(pl, st);
 }
 
 // Column slots of a launch with `left` columns to go: 8 / 4 / 2 share one pass over the weights (gemv_q_cols_kernel), 1 = one launch per column
@@ -301,31 +308,21 @@ int pm_launch_gemv(const pm_gemv_args & a, hipStream_t st) {
         f.job[0].type = a.type; f.job[0].N = a.N; f.job[0].W = a.W; f.job[0].W2 = a.W2;
         f.job[0].y = a.y + (size_t) c * a.y_stride; f.job[0].bias = a.bias;
         f.job[0].resid = a.resid ? a.resid + (size_t) c * a.y_stride : nullptr;
+        pm_gemv_plan pl;                                  // one plan per column group, whichever kernel takes it
+        int rc = pm_gemv_fused_plan(f, 0, pl); if (rc) return rc;
         const int left = a.ncols - c;
-        const bool pair = a.W2 != nullptr;
-        int nc = a.dbg_int ? 1 : pm_gemv_col_slots(a.type, pair, left);
+        int nc = a.dbg_int ? 1 : pm_gemv_col_slots(a.type, pl.pair, left);
+        // LDS: nc activation columns + nc results per row
+        const size_t col = pm_gemv_act_lds(a.K, pm_block_len(pl.ta)), rows = (size_t) ((a.N + pl.grid - 1) / pl.grid + 4);
+        while (nc > 1 && nc * col + rows * nc * 4 > 150 * 1024) nc /= 2;
+        int served = 1;
         if (nc > 1) {
-            GemvP p; int ta, tb, grid; bool pr; size_t lds1;
-            int rc = gemv_fill(f, 0, p, ta, tb, pr, lds1, grid);
-            if (rc) return rc;
-            // LDS: nc activation columns + nc results per row
-            const int ablk = pm_block_len(ta);
-            const size_t col = (size_t) ((a.K + 15) & ~15) + (size_t) (a.K / 16) * 4 + (size_t) ((a.K / ablk + 3) & ~3) * 4;
-            const size_t rows = (size_t) ((a.N + grid - 1) / grid + 4);
-            while (nc > 1 && nc * col + rows * nc * 4 > 150 * 1024) nc /= 2;
-            if (nc > 1) {
-                const int served = left < nc ? left : nc;
-                p.ncols = served; p.xq_stride = (long) xrow; p.y_stride = (long) a.y_stride;
-                const size_t lds = nc * col + rows * nc * 4;
-                rc = pm_launch_gemv_cols(ta, p, nc, pair, grid, lds, st);      // mmvq_cols.hip (512-thread workgroups, 256-VGPR budget)
-                if (rc) return rc;
-                c += served;
-                continue;
-            }
-        }
-        const int rc = pm_launch_gemv_fused(f, st);
+            served = left < nc ? left : nc;
+            pl.p.ncols = served; pl.p.xq_stride = (long) xrow; pl.p.y_stride = (long) a.y_stride;
+            rc = pm_launch_gemv_cols(pl.ta, pl.p, nc, pl.pair, pl.grid, nc * col + rows * nc * 4, st);      // mmvq_cols.hip (512-thread workgroups, 256-VGPR budget)
+        } else rc = gemv_launch_plan(pl, st);
         if (rc) return rc;
-        c += 1;
+        c += served;
     }
     return 0;
 }

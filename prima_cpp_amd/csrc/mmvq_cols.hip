@@ -28,7 +28,7 @@ __global__ __launch_bounds__(PM_GEMV_BLOCK, 2) void gemv_q_cols_kernel(GemvP p_i
 template <int T>
 int launch_cols(const GemvP & p, int nc, bool pair, int grid, size_t lds, hipStream_t st) {
     auto go = [&](auto kern) {
-        (void) hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        pm_allow_big_lds((const void *) kern, lds);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(PM_GEMV_BLOCK), lds, st, p);
     };
     if (pair) {                                       // ffn_gate | ffn_up of a 2-token step: silu(gate) * up per column, one pass over both matrices
@@ -46,7 +46,7 @@ int launch_cols(const GemvP & p, int nc, bool pair, int grid, size_t lds, hipStr
 
 }  // namespace
 
-// p: filled by gemv_fill (mmvq.hip) for ONE job, with ncols (the columns of the batch, <= nc: the kernel's column slots) / xq_stride / y_stride set;
+// p: filled by pm_gemv_fused_plan (mmvq.hip) for ONE job, with ncols (the columns of the batch, <= nc: the kernel's column slots) / xq_stride / y_stride set;
 // grid = one workgroup per CU
 int pm_launch_gemv_cols(int type, const GemvP & p, int nc, bool pair, int grid, size_t lds, hipStream_t st) {
     switch (type) {

@@ -14,17 +14,6 @@ namespace pmv {
 // only, and pm_gemv_col_slots (mmvq.hip) asks for it for them only
 constexpr uint32_t GEMV_PAIR_COLS_TYPES = pm_type_set(PM_Q4_K, PM_Q6_K);
 
-struct GemvJob {
-    const uint8_t * W; const uint8_t * W2; float * y; const float * bias; const float * resid;
-    long row_stride;
-    int N, is_b /*uses TB*/, U /*units per row*/;
-    int role;    // QKV epilogue (GemvP::epi): 0 none, 1 = query rows (rotate, round to F16), 2 = key rows (rotate, store in the K cache), 3 = value rows (store in the V cache)
-    int split;   // items of this job are (row, chunk) steps instead of whole rows: a few long rows spread over all waves (wk / wv next to wq)
-    // NEOX rope in the QKV epilogue (build_qwen2): a rotation pair is (i, i + n_rot / 2) of one head (ggml.c:14238-14253), so a workgroup's slice of
-    // s = 2^nx_s rows is made of TWO runs of s / 2 rows, n_rot / 2 apart: logical row L of the job (what the item loops count in) is matrix row
-    // job_row(L). nx_s == 0: identity (NORM rope pairs adjacent rows; every other job).
-    int nx_s, nx_dh /*log2 head_dim*/, nx_hrot /*n_rot / 2*/;
-};
 // logical -> matrix row of a job (wave-uniform arithmetic: shifts and masks, head_dim and the slice size are powers of two)
 __device__ __forceinline__ int job_row(const GemvJob & jb, int L) {
     const int sh = jb.nx_s > 0 ? jb.nx_s : 1, half = 1 << (sh - 1);                // (branch-free: scalar selects, the row loops stay straight-line code)
@@ -32,35 +21,6 @@ __device__ __forceinline__ int job_row(const GemvJob & jb, int L) {
     const int m = (L - w) + q * half + (l < half ? l : jb.nx_hrot + l - half);
     return jb.nx_s > 0 ? m : L;
 }
-// RoPE + F16 KV store in the epilogue of the wq | wk | wv launch (NORM-mode rope: a pair = two adjacent rows of one workgroup's slice).
-// tab[i] = (cos, sin) of rotation pair i at this token's position, built once per token by rope_table_kernel (layer_ops.hip) with the
-// reference's running product (ggml_rope_cache_init, ggml.c:14117-14131); cell / sequence as in attn_device.h (dyn: ggml-graph mode).
-struct QkvEpi {
-    const float * tab; const int32_t * pos_ptr, * seq_ptr, * dyn; long seq_stride;
-    uint16_t * kc, * vc; int kv_dim /*Hkv * dh*/, dh, n_ctx, n_rot, v_rowmajor;
-    int neox;    // rotation pairs (i, i + n_rot / 2) instead of (2 i, 2 i + 1): the q / k jobs carry the row mapping (GemvJob::nx_s)
-    // attention in the tail (pm_qkv_epi::att_out): q = the rotated query rows this launch stores, wgs = workgroups per KV-head group (power of two)
-    float * att_out; const float * att_q; unsigned * att_ticket; int * att_err; float att_scale; int att_H, att_wgs;
-};
-struct GemvP {
-    GemvJob job[3];
-    const uint8_t * xq;                     // xmode 0: pre-quantized activation row (row-SoA Q8_K / Q8_0)
-    const float * xf; const float * norm_w; // xmode 1: f32 activation; xmode 2: rms_norm(xf) * norm_w first; xmode 3: the same with the
-                                            // sum of squares of xf taken from the PRODUCER's per-workgroup partials (ss_in[n_ss], see ss_out)
-    float eps;
-    // producer-side sum of squares (round 5): a single-job launch whose output row is the next launch's rms_norm input stores, per workgroup,
-    // the f64 sum of the f32-rounded squares of the rows it wrote (ss_out[blockIdx.x]); the consuming launch (xmode 3) adds the n_ss partials
-    // instead of reducing the row itself - its prologue loses the reduction pass and one workgroup barrier (ggml.c:11975-11980: the reference
-    // sums (ggml_float)(x[i] * x[i]) in f64; any order of these <= 2^15 terms agrees after the final rounding to f32, as for xmode 2)
-    double * ss_out; const double * ss_in; int n_ss;
-    int xmode, K;
-    int32_t * dbg;
-    int ncols;                              // activation columns served by one launch (xmode 0 only when > 1)
-    long xq_stride, y_stride;               // bytes between quantized activation rows; floats between output columns
-    unsigned long long * ts;                // measurement builds (-DPM_TS): this launch's timestamp slot, else null
-    QkvEpi epi;                             // used by the EPI instantiation only
-};
-
 // Per-type traits. A unit's NV values come in NV/16 groups of 16 CONTIGUOUS activations; group_base() gives the
 // activation index of group g. X holds the quantized activation slice of one unit.
 template <int NV> struct XT { uint32_t q[NV / 4]; int gs[NV / 16]; float yd; };
@@ -790,7 +750,7 @@ __device__ __forceinline__ void write_out_qkv(const GemvJob & jb, const QkvEpi &
         if (pr >= np) return;
         if (NX && jb.nx_s) {
             // NEOX (ggml_compute_forward_rope_f32, ggml.c:14238-14253): x0 = row p0, x1 = row p0 + n_rot / 2 of the same head; the slice holds both
-            // (logical rows pr and pr + np). n_rot == head_dim here (gemv_fill): every row of a q / k head is rotated.
+            // (logical rows pr and pr + np). n_rot == head_dim here (pm_gemv_fused_plan): every row of a q / k head is rotated.
             const int p0 = job_row(jb, r0 + pr), p1 = p0 + jb.nx_hrot;
             float o0 = row_result(jb, outbuf, ob, pr, cpr), o1 = row_result(jb, outbuf, ob, pr + np, cpr);
             if (jb.bias) { o0 += ld_g(jb.bias + p0); o1 += ld_g(jb.bias + p1); }
@@ -987,7 +947,7 @@ __device__ __forceinline__ void gemv_body(const GemvP & p, char * smem, double *
         write_out<MEGA, NC>(p.job[1], outbuf, r0_1, r1_1, ob_1, tid, p.y_stride, cpr_1, ncw);
         write_out<MEGA, NC>(p.job[2], outbuf, r0_2, r1_2, ob_2, tid, p.y_stride, cpr_2, ncw);
         if constexpr (SS && NC == 1 && !PAIR && !EPI) if (p.ss_out) {
-            // this workgroup's partial of the consumer's rms_norm (single-job launches: gemv_fill): rows sit in threads 0 .. r1 - r0 - 1
+            // this workgroup's partial of the consumer's rms_norm (single-job launches: pm_gemv_fused_plan): rows sit in threads 0 .. r1 - r0 - 1
             const double ws = wave_sum_f64(ss);
             if (r1_0 - r0_0 <= 64) {                   // (every 70B / 8B / 72B shape: 16-32 rows per workgroup -> wave 0 alone, no barrier)
                 if (tid == 0) st_g(p.ss_out + b, ws);
@@ -1008,9 +968,6 @@ __device__ __forceinline__ void gemv_body(const GemvP & p, char * smem, double *
     pm_ts_store(p.ts, 1 | (PAIR ? 16 : 0) | (p.xmode << 8) | (p.K << 12), tsv);
 }
 
-
-// host side (mmvq.hip): validate a fused job list and fill the kernel argument block
-int gemv_fill(const pm_gemv_fused & a, int grid_fixed, GemvP & p, int & ta, int & tb, bool & pair, size_t & lds, int & grid);
 
 } // namespace pmv
 

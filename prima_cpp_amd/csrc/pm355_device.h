@@ -173,7 +173,7 @@ __device__ __forceinline__ void pm_ts_store(unsigned long long * ts, int tag, co
 }
 
 // ---- device-coherent activation traffic inside one launch ------------------------------------------------------
-// Activations written by one workgroup and read by another INSIDE one kernel (attn_wo.hip) go through agent-scope
+// Activations written by one workgroup and read by another INSIDE one kernel (the attention in a launch's tail, the flash forms' merge) go through agent-scope
 // relaxed atomics: global_load / global_store ... sc1, which are coherent across the 8 XCD L2s without any cache
 // write-back / invalidate. COH = false: plain accesses (stand-alone launches: kernel boundaries do the maintenance).
 // (loads: SYSTEM scope = `sc0 sc1` - an `sc1` load may be served from a line this XCD's L2 kept from an earlier read of the same buffer in the same

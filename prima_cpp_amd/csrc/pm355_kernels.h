@@ -84,7 +84,7 @@ struct pm_gemv_job {
     float * y; const float * bias; const float * resid;
 };
 // RoPE + KV store in the epilogue of a wq | wk | wv launch (jobs in that order). Served for NORM-mode rope when every workgroup's row
-// slices start and end on even rows (pm_gemv_fused_check tells); tab = this token's cos / sin table (pm_launch_rope_table)
+// slices start and end on even rows (pm_gemv_fused_plan tells); tab = this token's cos / sin table (pm_launch_rope_table)
 struct pm_qkv_epi {
     const float * tab; const int32_t * pos, * seq, * dyn; long seq_stride;
     void * kc, * vc; int Hkv, dh, n_ctx, n_rot, v_rowmajor;
@@ -104,13 +104,65 @@ struct pm_gemv_fused {
     int32_t * dbg_int;
     const pm_qkv_epi * epi;             // null: plain outputs
     // producer-side sum of squares for the NEXT launch's rms_norm (round 5): ss_out != null (single job, no pair, no epilogue) - every workgroup
-    // stores the f64 sum of the f32-rounded squares of the output rows it wrote into ss_out[workgroup] (pm_gemv_fused_grid() of them);
+    // stores the f64 sum of the f32-rounded squares of the output rows it wrote into ss_out[workgroup] (pm_gemv_plan::grid of them);
     // ss_in != null (with norm_w): the n_ss <= 256 partials a producer left for THIS launch's input row replace the in-kernel reduction
     double * ss_out; const double * ss_in; int n_ss;
 };
-int pm_launch_gemv_fused(const pm_gemv_fused & a, hipStream_t st);
-int pm_gemv_fused_check(const pm_gemv_fused & a);      // the validation part of pm_launch_gemv_fused only
-int pm_gemv_fused_grid(const pm_gemv_fused & a);       // workgroups pm_launch_gemv_fused would launch (= partials written through ss_out), or < 0
+namespace pmv {     // the kernel argument block of the mat-vec: mmvq_device.h reads it, pm_gemv_fused_plan fills it, pm_gemv_plan holds it
+struct GemvJob {
+    const uint8_t * W; const uint8_t * W2; float * y; const float * bias; const float * resid;
+    long row_stride;
+    int N, is_b /*uses TB*/, U /*units per row*/;
+    int role;    // QKV epilogue (GemvP::epi): 0 none, 1 = query rows (rotate, round to F16), 2 = key rows (rotate, store in the K cache), 3 = value rows (store in the V cache)
+    int split;   // items of this job are (row, chunk) steps instead of whole rows: a few long rows spread over all waves (wk / wv next to wq)
+    // NEOX rope in the QKV epilogue (build_qwen2): a rotation pair is (i, i + n_rot / 2) of one head (ggml.c:14238-14253), so a workgroup's slice of
+    // s = 2^nx_s rows is made of TWO runs of s / 2 rows, n_rot / 2 apart: logical row L of the job (what the item loops count in) is matrix row
+    // job_row(L). nx_s == 0: identity (NORM rope pairs adjacent rows; every other job).
+    int nx_s, nx_dh /*log2 head_dim*/, nx_hrot /*n_rot / 2*/;
+};
+// RoPE + F16 KV store in the epilogue of the wq | wk | wv launch (NORM-mode rope: a pair = two adjacent rows of one workgroup's slice).
+// tab[i] = (cos, sin) of rotation pair i at this token's position, built once per token by rope_table_kernel (layer_ops.hip) with the
+// reference's running product (ggml_rope_cache_init, ggml.c:14117-14131); cell / sequence as in attn_device.h (dyn: ggml-graph mode).
+struct QkvEpi {
+    const float * tab; const int32_t * pos_ptr, * seq_ptr, * dyn; long seq_stride;
+    uint16_t * kc, * vc; int kv_dim /*Hkv * dh*/, dh, n_ctx, n_rot, v_rowmajor;
+    int neox;    // rotation pairs (i, i + n_rot / 2) instead of (2 i, 2 i + 1): the q / k jobs carry the row mapping (GemvJob::nx_s)
+    // attention in the tail (pm_qkv_epi::att_out): q = the rotated query rows this launch stores, wgs = workgroups per KV-head group (power of two)
+    float * att_out; const float * att_q; unsigned * att_ticket; int * att_err; float att_scale; int att_H, att_wgs;
+};
+struct GemvP {
+    GemvJob job[3];
+    const uint8_t * xq;                     // xmode 0: pre-quantized activation row (row-SoA Q8_K / Q8_0)
+    const float * xf; const float * norm_w; // xmode 1: f32 activation; xmode 2: rms_norm(xf) * norm_w first; xmode 3: the same with the
+                                            // sum of squares of xf taken from the PRODUCER's per-workgroup partials (ss_in[n_ss], see ss_out)
+    float eps;
+    // producer-side sum of squares (round 5): a single-job launch whose output row is the next launch's rms_norm input stores, per workgroup,
+    // the f64 sum of the f32-rounded squares of the rows it wrote (ss_out[blockIdx.x]); the consuming launch (xmode 3) adds the n_ss partials
+    // instead of reducing the row itself - its prologue loses the reduction pass and one workgroup barrier (ggml.c:11975-11980: the reference
+    // sums (ggml_float)(x[i] * x[i]) in f64; any order of these <= 2^15 terms agrees after the final rounding to f32, as for xmode 2)
+    double * ss_out; const double * ss_in; int n_ss;
+    int xmode, K;
+    int32_t * dbg;
+    int ncols;                              // activation columns served by one launch (xmode 0 only when > 1)
+    long xq_stride, y_stride;               // bytes between quantized activation rows; floats between output columns
+    unsigned long long * ts;                // measurement builds (-DPM_TS): this launch's timestamp slot, else null
+    QkvEpi epi;                             // used by the EPI instantiation only
+};
+}
+struct pm_gemv_form { int pair, dbg, epi, npre, feat, xm, hot; };      // gemv_q_kernel<TA, TB, PAIR, DBG, EPI, NPRE, FEAT, XM, HOT>: a row of PM_GEMV_FORMS (mmvq.hip)
+// What pm_launch_gemv_fused will launch for a job list: the filled argument block, the (ta, tb) pair of PM_GEMV_TYPE_PAIRS (job 0 of the block is a `ta` job;
+// `first` = the input job that went there), the grid, the dynamic LDS bytes and the kernel form. Host arithmetic only, no pointer is followed.
+struct pm_gemv_plan { pmv::GemvP p; int ta, tb, pair, grid, first, row /*of PM_GEMV_FORMS*/; size_t lds; pm_gemv_form form; };
+// LDS bytes of one quantized activation column of K values with ablk-value scale blocks: int8 values | 16-group sums | block scales
+static inline size_t pm_gemv_act_lds(int K, int ablk) { return (size_t) ((K + 15) & ~15) + (size_t) (K / 16) * 4 + (size_t) ((K / ablk + 3) & ~3) * 4; }
+// Return codes of the mat-vec launchers (pm_gemv_fused_plan, pm_launch_gemv_fused, pm_launch_gemv; pm_eng_plan_add_matvec passes them on): 0 served;
+//   -1 a weight type or type mix no kernel is instantiated for, pair jobs next to plain ones, a debug launch with the epilogue; -2 K is no multiple of the
+//   type's block length; -4 the activation (or the attention tail) does not fit 150 KB of LDS; -5 the RoPE + KV-store epilogue does not serve the list (not
+//   three plain jobs, rows per workgroup not whole rotation pairs, head / NEOX slice conditions); -6 sum-of-squares arguments (ss_in without norm_w / with xq /
+//   n_ss outside 1..256, ss_out on anything but ONE plain job, either with a debug launch); -7 attention tail (grid no power-of-two run per KV head, head_dim,
+//   position-pointer mode, transposed V cache, wq Q4_K); -8 sum of squares / tail asked of the product library (PM_EXPERIMENTS only); -9 njobs outside 1..3
+int pm_gemv_fused_plan(const pm_gemv_fused & a, int cus, pm_gemv_plan & out);     // cus <= 0: the current device's CU count
+int pm_launch_gemv_fused(const pm_gemv_fused & a, hipStream_t st);     // plan, then launch the plan
 
 // batched (prefill) GEMM on MFMA: up to 4 matrices W_j [N_j][K] (quantized, HBM layout) over the same activations x [T][K]. Job: Y[t * ldy + n] (f32) or, when
 // Yh != null, Yh[t * ldy + n] (F16; Y is not written) = W . x (+ bias[n]) (+ resid[t * ldy + n]) (* silu(silu_gate[t * ldy + n])); ldy == 0 means N.

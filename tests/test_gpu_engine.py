@@ -592,3 +592,31 @@ def test_attention_tail_decode_is_bit_identical(E, monkeypatch, arch):
         w.close()
     for i, ((h0, l0), (h1, l1)) in enumerate(zip(*outs)):
         assert np.array_equal(h0, h1) and np.array_equal(l0, l1), i
+
+
+def test_single_token_decode_with_three_types_in_wq_wk_wv_vs_oracle(E, oracle):
+    """wq Q4_K, wk Q6_K, wv Q5_K: three types, so neither the epilogue nor the three-job launch serves wq | wk | wv and the step falls back to one
+    mat-vec launch per matrix (run_layers_fused) - single tokens from an empty cache, at the tolerances of test_window_prefill_and_decode_vs_oracle."""
+    from _bind import Q5_K
+    torch = E.torch
+    rng = np.random.default_rng(77)
+    d = tiny_model(rng, arch=0, n_layer=2, n_embd=512, n_head=8, n_head_kv=8, n_ff=512, n_vocab=320, n_ctx=64, rope_freqs=True,
+                   types={"attn_k": Q6_K, "attn_v": Q5_K}, quantize=_quantizer())
+    w = E.Window(_hp(d), n_ctx=64)
+    w.load_desc(d)
+    w.finalize(max_tokens=1)
+    ho = oracle.model_new(d)
+    toks = rng.integers(0, d.n_vocab, 4).astype(np.int32)
+    for p0, t in enumerate(toks):
+        hid, lg, am = w.decode(tokens=torch.from_numpy(toks[p0:p0 + 1]).cuda(), pos0=p0, want_argmax=True)
+        h_ref, l_ref = oracle.model_eval(ho, d, tokens=toks[p0:p0 + 1], pos0=p0)
+        print(f"[three-type wq | wk | wv] token {p0}: NMSE hidden {_nmse(hid.cpu().numpy(), h_ref):.2e} logits {_nmse(lg.cpu().numpy(), l_ref):.2e}")
+        assert _nmse(hid.cpu().numpy(), h_ref) < 1e-3
+        assert _nmse(lg.cpu().numpy(), l_ref) < 1e-3
+        assert int(am.item()) == int(np.argmax(lg.cpu().numpy()))
+    for which in (0, 1):
+        a = w.kv(0, which).view(np.float16).astype(np.float32)
+        b = oracle.model_kv(ho, d, 0, which).view(np.float16).astype(np.float32)
+        assert _nmse(a, b) < 1e-6
+    oracle.model_free(ho)
+    w.close()

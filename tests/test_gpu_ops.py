@@ -1473,3 +1473,68 @@ def test_attn_token_f16_caches_cell_mask_and_each_layout_flag_alone(P, form, fla
         want = p @ V[:, hk * dh:(hk + 1) * dh].astype(np.float64)
         print(f"{form} flags {flags} head {h}: max |d out| {np.abs(out[h] - want).max():.3g}, max |out| {np.abs(want).max():.3g}")
         assert np.abs(out[h] - want).max() <= 2e-3 * np.abs(want).max() + 1e-4, h
+
+
+# ---- every kernel form of the single-token mat-vec against the launch that just misses it --------------------------------------------------------
+# The HOT / XM forms of gemv_q_kernel (mmvq.hip) pin fields of their argument block; the launcher picks them from the block's contents. Each case
+# below runs the launch that takes such a form next to launches that compute the same values through another form - a bias of zeros, the
+# pre-quantized path behind the stand-alone rms_norm / quantize kernels, ggml-graph mode at the same cell, a row-major V cache - and asks for equal values.
+
+@pytest.mark.parametrize("K", [256, 768])
+@pytest.mark.parametrize("t", [Q4_K, Q5_K, Q6_K, Q8_0])
+def test_matvec_single_job_forms_against_their_near_misses(P, t, K):
+    torch = P.torch
+    rng = np.random.default_rng(1200 + t + K)
+    N = 33
+    w, w2, wb = (P.upload_weight(t, rand_blocks(t, n, K, rng), K, n) for n in (N, N, 40))
+    x = _dev(P, rng.normal(0, 1.5, (1, K)).astype(np.float32))
+    nw = _dev(P, (1 + rng.normal(0, 0.05, K)).astype(np.float32))
+    resid, resid_b = _dev(P, rng.normal(0, 1, N).astype(np.float32)), _dev(P, rng.normal(0, 1, 40).astype(np.float32))
+    zeros = torch.zeros(N, dtype=torch.float32, device="cuda")
+    xn = P.rms_norm(x, nw, 1e-5)
+    # wo / ffn_down: f32 row + residual (HOT) | + a bias of zeros (XM 1) | pre-quantized (plain form) | next to a second job (XM 1)
+    hot = P.mul_mat_vec_fused([w], x, resids=[resid])[0]
+    assert torch.equal(hot, P.mul_mat_vec_fused([w], x, biases=[zeros], resids=[resid])[0])
+    assert torch.equal(hot, P.mul_mat_vec(w, x=x, resid=resid.view(1, -1))[0])
+    two = P.mul_mat_vec_fused([w, wb], x, resids=[resid, resid_b])
+    assert torch.equal(hot, two[0]) and torch.equal(two[1], P.mul_mat_vec_fused([wb], x, resids=[resid_b])[0])
+    # no residual: f32 row (XM 1) | pre-quantized; rms_norm'ed row (XM 2) | stand-alone rms_norm + pre-quantized
+    assert torch.equal(P.mul_mat_vec_fused([w], x)[0], P.mul_mat_vec(w, x=x)[0])
+    assert torch.equal(P.mul_mat_vec_fused([w], x, norm_w=nw, eps=1e-5, resids=[resid])[0], P.mul_mat_vec(w, x=xn, resid=resid.view(1, -1))[0])
+    # ffn_gate | ffn_up: rms_norm'ed row (HOT) | + a bias of zeros (XM 2) | + a residual of zeros (XM 2) | pre-quantized (plain); f32 row (plain) | pre-quantized
+    hot = P.mul_mat_vec_fused([w], x, norm_w=nw, eps=1e-5, w2s=[w2])[0]
+    assert torch.equal(hot, P.mul_mat_vec_fused([w], x, norm_w=nw, eps=1e-5, w2s=[w2], biases=[zeros])[0])
+    assert torch.equal(hot, P.mul_mat_vec_fused([w], x, norm_w=nw, eps=1e-5, w2s=[w2], resids=[zeros])[0])
+    assert torch.equal(hot, P.mul_mat_vec(w, x=xn, w2=w2)[0])
+    assert torch.equal(P.mul_mat_vec_fused([w], x, w2s=[w2])[0], P.mul_mat_vec(w, x=x, w2=w2)[0])
+
+
+@pytest.mark.parametrize("tv", [Q4_K, Q6_K, Q5_K])
+def test_matvec_qkv_epilogue_forms_against_their_near_misses(P, tv):
+    """wq | wk | wv with the RoPE + KV-store epilogue at the smallest shape it serves on 256 CUs (K 512, three matrices of 512 rows, head_dim 64):
+    position-pointer mode (HOT 1) | ggml-graph mode at the same cell (HOT 2) | each with a bias of zeros (XM 2) | a row-major V cache, compared
+    transposed (XM 2) | the row normalized by the stand-alone kernel first (plain epilogue form)."""
+    torch = P.torch
+    rng = np.random.default_rng(1300 + tv)
+    K, N, Hkv, dh, n_ctx, cell = 512, 512, 8, 64, 16, 5
+    ws = [P.upload_weight(t, rand_blocks(t, N, K, rng), K, N) for t in (Q4_K, Q4_K, tv)]
+    if P.mul_mat_vec_qkv_check(ws, Hkv, dh) != 0:
+        pytest.skip("the epilogue needs N % (2 * CUs) == 0: not this device")
+    x = _dev(P, rng.normal(0, 1, (1, K)).astype(np.float32))
+    nw = _dev(P, (1 + rng.normal(0, 0.05, K)).astype(np.float32))
+    zeros = [torch.zeros(N, dtype=torch.float32, device="cuda") for _ in range(3)]
+    pd = torch.tensor([cell], dtype=torch.int32, device="cuda")
+    dyn = torch.tensor([cell, cell + 1], dtype=torch.int32, device="cuda")
+    tab = P.rope_table(pd, dh, freq_base=500000.0)
+
+    def run(xin, norm_w, pos, cell_nkv, biases=None, v_rowmajor=False):
+        kc = torch.zeros(n_ctx * N, dtype=torch.int16, device="cuda"); vc = torch.zeros_like(kc)
+        q = P.mul_mat_vec_qkv(ws, xin, tab, pos, kc, vc, Hkv, dh, n_ctx, norm_w=norm_w, eps=1e-5, biases=biases, cell_nkv=cell_nkv, v_rowmajor=v_rowmajor)
+        return q, kc, (vc.view(n_ctx, N).t().contiguous().view(-1) if v_rowmajor else vc)
+
+    hot = run(x, nw, pd, None)
+    assert hot[1].view(n_ctx, N)[cell].any() and hot[2].view(N, n_ctx)[:, cell].any() and not hot[1].view(n_ctx, N)[cell + 1].any()
+    for name, got in (("ggml-graph mode", run(x, nw, None, dyn)), ("bias of zeros", run(x, nw, pd, None, biases=zeros)),
+                      ("ggml-graph mode, bias of zeros", run(x, nw, None, dyn, biases=zeros)), ("row-major V cache", run(x, nw, pd, None, v_rowmajor=True)),
+                      ("stand-alone rms_norm", run(P.rms_norm(x, nw, 1e-5), None, pd, None))):
+        assert all(torch.equal(a, b) for a, b in zip(hot, got)), name
