@@ -360,9 +360,11 @@ PM355_API int pm355_mul_mat_vec_qkv_check_ex(const pm355_matvec_job * jobs, int6
  * arithmetic, no device needed and no pointer followed (a job's W2 / bias / resid and the store's pointers only count as null or not). x_mode: 0 a
  * pre-quantized activation row, 1 an f32 row, 2 rms_norm of an f32 row, 3 the same from producer-side partials; + 4 the debug launch, + 8 with sumsq_out.
  * qkv != NULL: the RoPE + KV-store epilogue. Returns 0 or the launcher's own refusal - NOT a PM355_E_* code, and no pm355_last_error text - (-1 type mix, -2 K,
- * -4 LDS, -5 epilogue, -6 sum-of-squares arguments, -7 attention tail, -8 experiments library only, -9 job count or another argument of this call) and fills the first n_out of out[19] = {workgroups, LDS bytes, type of the first job in
+ * -4 LDS, -5 epilogue, -6 sum-of-squares arguments, -7 attention tail, -8 experiments library only, -9 job count or another argument of this call) and fills the first n_out of out[25] = {workgroups, LDS bytes, type of the first job in
  * the kernel's order, second type, pair launch, which input job runs first, split[3] and log2 NEOX slice[3] of the jobs in the kernel's order, and the
- * kernel form <PAIR, DBG, EPI, NPRE, FEAT (1 sum of squares, 2 attention tail, 4 NEOX), XM, HOT> of gemv_q_kernel (prima_cpp_amd/csrc/mmvq.hip)}. */
+ * kernel form <PAIR, DBG, EPI, NPRE, FEAT (1 sum of squares, 2 attention tail, 4 NEOX), XM, HOT> of gemv_q_kernel (prima_cpp_amd/csrc/mmvq.hip); behind
+ * these 19: rows per workgroup N / workgroups of the three jobs in the kernel's order, then their multipliers m (read as uint32): workgroup b starts a job
+ * at row b * (N / workgroups) + ((uint64) b * m >> 32) = floor(N * b / workgroups); m == 0 when the workgroups divide N}. */
 PM355_API int pm355_mul_mat_vec_fused_plan(const pm355_matvec_job * jobs, int njobs, int64_t K, int x_mode, const pm355_qkv_store * qkv, int n_cus,
                                            int32_t * out, int n_out);
 PM355_API int pm355_attn_cached(const float * q_rot, void * k_cache, void * v_cache, const int32_t * d_pos, const int32_t * d_cell_nkv,

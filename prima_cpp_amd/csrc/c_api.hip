@@ -527,9 +527,12 @@ int pm355_mul_mat_vec_fused_plan(const pm355_matvec_job * jobs, int njobs, int64
     pm_gemv_plan pl;
     if (const int rc = pm_gemv_fused_plan(f, n_cus, pl)) return rc;
     const pmv::GemvJob * j = pl.p.job;
-    const int32_t v[19] = {pl.grid, (int32_t) pl.lds, pl.ta, pl.tb, pl.pair, pl.first, j[0].split, j[1].split, j[2].split, j[0].nx_s, j[1].nx_s, j[2].nx_s,
-                           pl.form.pair, pl.form.dbg, pl.form.epi, pl.form.npre, pl.form.feat, pl.form.xm, pl.form.hot};
-    for (int i = 0; i < n_out && i < 19; ++i) out[i] = v[i];
+    // [19..24]: the slice arithmetic of the three jobs of the block (GemvJob::rpw, then GemvJob::rmul as its bit pattern): workgroup b starts job j at row
+    // b * rpw[j] + ((uint64) b * rmul[j] >> 32)
+    const int32_t v[25] = {pl.grid, (int32_t) pl.lds, pl.ta, pl.tb, pl.pair, pl.first, j[0].split, j[1].split, j[2].split, j[0].nx_s, j[1].nx_s, j[2].nx_s,
+                           pl.form.pair, pl.form.dbg, pl.form.epi, pl.form.npre, pl.form.feat, pl.form.xm, pl.form.hot,
+                           j[0].rpw, j[1].rpw, j[2].rpw, (int32_t) j[0].rmul, (int32_t) j[1].rmul, (int32_t) j[2].rmul};
+    for (int i = 0; i < n_out && i < 25; ++i) out[i] = v[i];
     return 0;
 }
 int pm355_mul_mat_vec_qkv_check(const pm355_matvec_job * jobs, int64_t K, int n_head_kv, int head_dim, int n_rot) {

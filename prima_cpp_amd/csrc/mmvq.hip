@@ -43,9 +43,12 @@ PM_GEMV_TYPE_PAIRS(PM_QT_IS)
 
 namespace {
 
-// The first things a workgroup does - the activation loads and the pre-issued weight loads of job 0 - need six values of the argument block. They
-// travel as LEADING scalar kernel arguments as well, which the dispatcher preloads into SGPRs (-mllvm -amdgpu-kernarg-preload-count, build.py):
-// the wave starts issuing its loads without first waiting for an s_load of the kernarg segment (a by-value struct is never preloaded).
+// The first things a workgroup does - the activation loads and the pre-issued weight loads of job 0 - need these values of the argument block: the
+// activation, job 0's matrix (its row stride as an int: a row of K <= 122880 values is far below 2 GB) and job 0's slice arithmetic (GemvJob::rpw /
+// rmul) - fourteen dwords, all that can be preloaded: sixteen user SGPRs less the two of the kernarg segment pointer. They travel as LEADING
+// scalar kernel arguments as well, which the dispatcher preloads into SGPRs (-mllvm -amdgpu-kernarg-preload-count, build.py): the wave issues its loads
+// without first waiting for an s_load of the kernarg segment (a by-value struct is never preloaded; neither is gridDim.x, a hidden argument - the
+// kernels do not read it). gemv_body issues them before it touches anything else of the block.
 // FEAT (mmvq_device.h): PM_FEAT_SS / PM_FEAT_TAIL code lives in instantiations of its own - a launch that uses neither runs the plain kernel
 // XM >= 0: the activation mode is a compile-time constant of the instantiation (the hot launches: 1 = f32 row, 2 = rms_norm of an f32 row) - the prologue
 // keeps one mode's code instead of four behind scalar branches
@@ -58,13 +61,14 @@ __global__ __launch_bounds__(PM_GEMV_BLOCK, 4) void gemv_q_kernel(GemvP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ double nred[PM_GEMV_NW];
 #else
-__global__ __launch_bounds__(PM_GEMV_BLOCK, 4) void gemv_q_kernel(const float * xf, const float * norm_w, const uint8_t * W0, const uint8_t * W0b, long row_stride0,
-                                                                  int K, int xmode, int N0, int U0, GemvP p_in) {
+__global__ __launch_bounds__(PM_GEMV_BLOCK, 4) void gemv_q_kernel(const float * xf, const float * norm_w, const uint8_t * W0, const uint8_t * W0b, int row_stride0,
+                                                                  int K, int xmode, int U0, int rpw0, unsigned rmul0, GemvP p_in) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ double nred[PM_GEMV_NW];
     GemvP p = p_in;
     p.xf = xf; p.norm_w = norm_w; p.K = K; p.xmode = xmode;
-    p.job[0].W = W0; p.job[0].W2 = W0b; p.job[0].row_stride = row_stride0; p.job[0].N = N0; p.job[0].U = U0;
+    p.job[0].W = W0; p.job[0].W2 = W0b; p.job[0].row_stride = row_stride0; p.job[0].U = U0;
+    p.job[0].rpw = rpw0; p.job[0].rmul = rmul0;
 #endif
     if constexpr (XM >= 0) p.xmode = XM;
     if constexpr (HOT) {
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(PM_GEMV_BLOCK, 4) void gemv_q_kernel(const float * 
             p.job[0].role = 1; p.job[1].role = 2; p.job[2].role = 3;                    // wq, wk, wv in this order (no TA-first swap happened)
             p.job[0].is_b = 0; p.job[1].is_b = 0; p.job[2].is_b = TA != TB ? 1 : 0;     // Q4_K_M: wq / wk of the first type, wv of the second (or all of one)
             p.job[0].split = 0; p.job[0].resid = nullptr; p.job[1].resid = nullptr; p.job[2].resid = nullptr;
-        } else { p.job[1].N = 0; p.job[2].N = 0; p.job[0].split = 0; p.job[0].is_b = 0; p.job[0].role = 0; }
+        } else { p.job[1].N = 0; p.job[2].N = 0; p.job[1].rpw = 0; p.job[2].rpw = 0; p.job[1].rmul = 0; p.job[2].rmul = 0; p.job[0].split = 0; p.job[0].is_b = 0; p.job[0].role = 0; }
         if constexpr (PAIR) p.job[0].resid = nullptr;
         if constexpr (!PAIR && !EPI) __builtin_assume(p.job[0].resid != nullptr);     // wo / ffn_down: always + residual
     }
@@ -211,7 +215,8 @@ int pm_gemv_fused_plan(const pm_gemv_fused & a, int cus, pm_gemv_plan & out) {
     int grid = (1024 / PM_GEMV_BLOCK) * (cus > 0 ? cus : pm_device_cus());
     long tot_rows = 0;
     for (int j = 0; j < a.njobs; ++j) tot_rows += a.job[j].N;
-    while ((tot_rows + grid - 1) / grid + 3 > PM_MAX_ROWS_PER_WG) grid *= 2;
+    while ((tot_rows + grid - 1) / grid + 3 > PM_MAX_ROWS_PER_WG && grid < 65536) grid *= 2;
+    if (grid >= 65536) return -2;                                     // (over 33 million rows: GemvJob::rmul is exact below that)
     for (int j = 0; j < 3; ++j) {
         GemvJob & g = p.job[j];
         if (j >= a.njobs) { g.N = 0; continue; }
@@ -219,6 +224,10 @@ int pm_gemv_fused_plan(const pm_gemv_fused & a, int cus, pm_gemv_plan & out) {
         const int nv = pm_type_info(s.type).nv;
         g.W = (const uint8_t *) s.W; g.W2 = (const uint8_t *) s.W2; g.y = s.y; g.bias = s.bias; g.resid = s.resid;
         g.N = s.N; g.is_b = (s.type != ta); g.U = a.K / nv;
+        // the slices [floor(N b / grid), floor(N (b + 1) / grid)) as a multiply and a multiply-high. With rem = N % grid and eps = rmul * grid - 2^32 * rem
+        // (0 <= eps < grid): b * rmul / 2^32 = b * rem / grid + b * eps / (grid * 2^32), and the last term stays under 1 / grid - it cannot carry the
+        // fraction of b * rem / grid (at most (grid - 1) / grid) over the next integer - as long as b * eps < 2^32, which b <= grid < 65536 guarantees
+        g.rpw = s.N / grid; g.rmul = (unsigned) ((((unsigned long long) (s.N % grid) << 32) + (unsigned) grid - 1) / (unsigned) grid);
         g.row_stride = (long) pm_weight_row_stride(s.type, a.K);
         g.role = 0; g.split = 0;
         if (a.epi) {
@@ -278,7 +287,8 @@ static int gemv_launch_plan(pm_gemv_plan & pl, hipStream_t st) {
 #ifdef PM_NO_PRELOAD_ARGS
     hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(PM_GEMV_BLOCK), pl.lds, st, p);
 #else
-    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(PM_GEMV_BLOCK), pl.lds, st, p.xf, p.norm_w, p.job[0].W, p.job[0].W2, p.job[0].row_stride, p.K, p.xmode, p.job[0].N, p.job[0].U, p);
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(PM_GEMV_BLOCK), pl.lds, st, p.xf, p.norm_w, p.job[0].W, p.job[0].W2, (int) p.job[0].row_stride, p.K, p.xmode, p.job[0].U,
+                       p.job[0].rpw, p.job[0].rmul, p);
 #endif
     return 0;
 }

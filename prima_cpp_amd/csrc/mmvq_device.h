@@ -825,6 +825,10 @@ __device__ __forceinline__ void qkv_attention_tail(const GemvP & p, char * smem,
     else attn_tail_head<64>(a, h, smem + 64, bar4);
 }
 
+// first row of workgroup b's slice of a job = floor(N * b / grid), without the division and without the grid (GemvJob::rpw / rmul); b is wave-uniform:
+// a scalar multiply, a scalar multiply-high and an add
+__device__ __forceinline__ int slice_at(const GemvJob & jb, int b) { return b * jb.rpw + (int) __umulhi((unsigned) b, jb.rmul); }
+
 // The whole mat-vec of one workgroup (body of gemv_q_kernel / gemv_q_cols_kernel).
 template <int TA, int TB, bool PAIR, bool DBG, int NC = 1, bool EPI = false, int NPRE = 2, int FEAT = 0>
 __device__ __forceinline__ void gemv_body(const GemvP & p, char * smem, double * nred) {
@@ -842,16 +846,39 @@ __device__ __forceinline__ void gemv_body(const GemvP & p, char * smem, double *
     int *    xs_gs = (int *) (smem + ((p.K + 15) & ~15));               // [K/16]
     float *  xs_d  = (float *) (xs_gs + p.K / 16);                      // [K/ABLK]
     float *  outbuf = (float *) (smem + (size_t) NC * col_bytes);       // [sum of this workgroup's rows][NC]
-    const int b = blockIdx.x, G = gridDim.x, tid = threadIdx.x, lane = tid & 63;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     // wave index as a SCALAR: everything derived from it (row numbers, row base pointers, loop counters) then lives in
     // SGPRs and the weight loads use the saddr + 32-bit-voffset form instead of 64-bit VALU address arithmetic
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // this workgroup's slice [r0, r1) of every job, and the ITEM list = concatenation of the jobs' R-row groups
-    // this workgroup's slice [r0, r1) of every job (scalars, not arrays: a runtime-indexed array would live in scratch)
-    const int r0_0 = (int) ((long) p.job[0].N * b / G), r1_0 = (int) ((long) p.job[0].N * (b + 1) / G);
-    const int r0_1 = (int) ((long) p.job[1].N * b / G), r1_1 = (int) ((long) p.job[1].N * (b + 1) / G);
-    const int r0_2 = (int) ((long) p.job[2].N * b / G), r1_2 = (int) ((long) p.job[2].N * (b + 1) / G);
+    // (1) activation row -> LDS (quantized, bit-exact with the reference quantizers).
+    //     [Measured and rejected: pre-issuing the first item's 16-byte weight loads across the prologue (spills under the
+    //      128-VGPR budget, -20 %); an L2 prefetch of that item with one dword per 128-B line (-7 % even when limited to
+    //      the small wq/wo launches: the in-order VMEM return delays the prologue and the lines are fetched twice); and
+    //      splitting the workgroup into 8 prologue waves + 8 waves that pre-issue their first step (-3 %, A/B on one box).]
+    // ENTRY: the activation loads and job 0's pre-issued weight loads go out on what the dispatcher preloaded into SGPRs (gemv_q_kernel's leading
+    // arguments: the activation, job 0's matrix and slice arithmetic) - no wait for the kernarg segment, no division, no hidden argument in front of
+    // them. Everything that needs another field of the block - the slices of jobs 1 and 2, the item counts, the epilogue's cache cell - comes behind
+    // (the sched_barrier keeps the compiler from moving it, and the scalar-load wait it needs, back up): those round trips then run next to the
+    // activation's, which is the floor of the prologue anyway.
+    unsigned long long tsv[6] = {PM_TS_NOW(), 0, 0, 0, 0, 0};           // (measurement builds: taken before any argument is touched)
+    const int r0_0 = slice_at(p.job[0], b), r1_0 = slice_at(p.job[0], b + 1);      // this workgroup's slice [r0, r1) of job 0
+    ActRegsT<SS> areg;
+    stage_issue<ABLK, MEGA, SS>(p, areg, wave, lane);                             // activation loads go out first (they return first)
+    typename IA::Regs g0, g1;                                   // job 0 is always of type TA (host side orders the jobs)
+    {   // the first NPRE steps of this wave in job 0 (same cursor sequence as run_job: chunks of a row, then the wave's next item)
+        const int cpr0 = (((p.job[0].U + 63) >> 6) + IA::CH - 1) / IA::CH;
+        int prow = r0_0 + wave * R, pc = 0;
+        auto adv = [&]() __attribute__((always_inline)) { if (++pc == cpr0) { pc = 0; prow += PM_GEMV_NW * R; } };
+        IA::issue(g0, p, p.job[0], prow, r1_0, pc * IA::CH, lane); adv();
+        if (NPRE >= 2) { IA::issue(g1, p, p.job[0], prow, r1_0, pc * IA::CH, lane); adv(); }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long ts_issued = PM_TS_NOW();           // (measurement builds: the entry's loads are out)
+    // this workgroup's slice [r0, r1) of the other jobs (scalars, not arrays: a runtime-indexed array would live in scratch), and the ITEM list =
+    // concatenation of the jobs' R-row groups
+    const int r0_1 = slice_at(p.job[1], b), r1_1 = slice_at(p.job[1], b + 1);
+    const int r0_2 = slice_at(p.job[2], b), r1_2 = slice_at(p.job[2], b + 1);
     // split jobs (EPI launches: wk / wv): items = (row, chunk) steps, results = one partial per item
     const int cpr_1 = !EPI || !p.job[1].split ? 1 : (TA != TB && p.job[1].is_b ? job_cpr<TB>(p.job[1]) : job_cpr<TA>(p.job[1]));
     const int cpr_2 = !EPI || !p.job[2].split ? 1 : (TA != TB && p.job[2].is_b ? job_cpr<TB>(p.job[2]) : job_cpr<TA>(p.job[2]));
@@ -867,23 +894,6 @@ __device__ __forceinline__ void gemv_body(const GemvP & p, char * smem, double *
             epi_slot = uniform_const_ptr(p.epi.pos_ptr)[seq];
             epi_off = (long) seq * p.epi.seq_stride;
         }
-    }
-
-    // (1) activation row -> LDS (quantized, bit-exact with the reference quantizers).
-    //     [Measured and rejected: pre-issuing the first item's 16-byte weight loads across the prologue (spills under the
-    //      128-VGPR budget, -20 %); an L2 prefetch of that item with one dword per 128-B line (-7 % even when limited to
-    //      the small wq/wo launches: the in-order VMEM return delays the prologue and the lines are fetched twice); and
-    //      splitting the workgroup into 8 prologue waves + 8 waves that pre-issue their first step (-3 %, A/B on one box).]
-    unsigned long long tsv[6] = {PM_TS_NOW(), 0, 0, 0, 0, 0};
-    ActRegsT<SS> areg;
-    stage_issue<ABLK, MEGA, SS>(p, areg, wave, lane);                             // activation loads go out first (they return first)
-    typename IA::Regs g0, g1;                                   // job 0 is always of type TA (host side orders the jobs)
-    {   // the first NPRE steps of this wave in job 0 (same cursor sequence as run_job: chunks of a row, then the wave's next item)
-        const int cpr0 = (((p.job[0].U + 63) >> 6) + IA::CH - 1) / IA::CH;
-        int prow = r0_0 + wave * R, pc = 0;
-        auto adv = [&]() __attribute__((always_inline)) { if (++pc == cpr0) { pc = 0; prow += PM_GEMV_NW * R; } };
-        IA::issue(g0, p, p.job[0], prow, r1_0, pc * IA::CH, lane); adv();
-        if (NPRE >= 2) { IA::issue(g1, p, p.job[0], prow, r1_0, pc * IA::CH, lane); adv(); }
     }
     stage_finish<ABLK, MEGA, SS>(p, areg, xs_q, xs_gs, xs_d, nred, wave, lane, NC, col_bytes, &tsv[1]);
     __syncthreads();
@@ -965,7 +975,7 @@ __device__ __forceinline__ void gemv_body(const GemvP & p, char * smem, double *
         }
     }
     tsv[5] = PM_TS_NOW();
-    pm_ts_store(p.ts, 1 | (PAIR ? 16 : 0) | (p.xmode << 8) | (p.K << 12), tsv);
+    pm_ts_store(p.ts, 1 | (PAIR ? 16 : 0) | (p.xmode << 8) | (p.K << 12), tsv, ts_issued);
 }
 
 

@@ -161,13 +161,15 @@ unsigned long long * pm_ts_next_slot();          // host (ts.hip): device addres
 #define PM_TS_NOW() 0ull
 static inline unsigned long long * pm_ts_next_slot() { return nullptr; }
 #endif
-__device__ __forceinline__ void pm_ts_store(unsigned long long * ts, int tag, const unsigned long long (&t)[6]) {
+// issued (the mat-vec): the stamp taken once the entry's loads - activation and pre-issued weights - are out; it travels as ticks since t[0] in the upper
+// half of the slot's last word (the workgroup count keeps the lower half), 0 = not taken
+__device__ __forceinline__ void pm_ts_store(unsigned long long * ts, int tag, const unsigned long long (&t)[6], unsigned long long issued = 0) {
 #ifdef PM_TS
     if (ts && threadIdx.x == 0 && blockIdx.x < PM_TS_WGS) {
         unsigned long long * o = ts + (size_t) blockIdx.x * 8;
 #pragma unroll
         for (int i = 0; i < 6; ++i) o[i] = t[i];
-        o[6] = (unsigned long long) tag; o[7] = (unsigned long long) gridDim.x;
+        o[6] = (unsigned long long) tag; o[7] = (unsigned long long) gridDim.x | ((issued ? (issued - t[0]) & 0xffffffffull : 0ull) << 32);
     }
 #endif
 }

@@ -119,6 +119,10 @@ struct GemvJob {
     // s = 2^nx_s rows is made of TWO runs of s / 2 rows, n_rot / 2 apart: logical row L of the job (what the item loops count in) is matrix row
     // job_row(L). nx_s == 0: identity (NORM rope pairs adjacent rows; every other job).
     int nx_s, nx_dh /*log2 head_dim*/, nx_hrot /*n_rot / 2*/;
+    // This job's slice of workgroup b is [at(b), at(b + 1)), at(b) = floor(N * b / grid) = b * rpw + mulhi32(b, rmul) with rpw = N / grid and
+    // rmul = ceil(2^32 * (N % grid) / grid): exact for 0 <= b <= grid < 65536 (pm_gemv_fused_plan proves it and refuses larger grids). N % grid == 0 - every
+    // launch of a decode layer - gives rmul = 0, a plain multiply. The kernels neither divide nor read the grid size (pmv::slice_at, mmvq_device.h).
+    int rpw; unsigned rmul;
 };
 // RoPE + F16 KV store in the epilogue of the wq | wk | wv launch (NORM-mode rope: a pair = two adjacent rows of one workgroup's slice).
 // tab[i] = (cos, sin) of rotation pair i at this token's position, built once per token by rope_table_kernel (layer_ops.hip) with the
@@ -157,7 +161,7 @@ struct pm_gemv_plan { pmv::GemvP p; int ta, tb, pair, grid, first, row /*of PM_G
 static inline size_t pm_gemv_act_lds(int K, int ablk) { return (size_t) ((K + 15) & ~15) + (size_t) (K / 16) * 4 + (size_t) ((K / ablk + 3) & ~3) * 4; }
 // Return codes of the mat-vec launchers (pm_gemv_fused_plan, pm_launch_gemv_fused, pm_launch_gemv; pm_eng_plan_add_matvec passes them on): 0 served;
 //   -1 a weight type or type mix no kernel is instantiated for, pair jobs next to plain ones, a debug launch with the epilogue; -2 K is no multiple of the
-//   type's block length; -4 the activation (or the attention tail) does not fit 150 KB of LDS; -5 the RoPE + KV-store epilogue does not serve the list (not
+//   type's block length, or so many rows that the grid reaches 65536 workgroups (the slice arithmetic, GemvJob::rmul); -4 the activation (or the attention tail) does not fit 150 KB of LDS; -5 the RoPE + KV-store epilogue does not serve the list (not
 //   three plain jobs, rows per workgroup not whole rotation pairs, head / NEOX slice conditions); -6 sum-of-squares arguments (ss_in without norm_w / with xq /
 //   n_ss outside 1..256, ss_out on anything but ONE plain job, either with a debug launch); -7 attention tail (grid no power-of-two run per KV head, head_dim,
 //   position-pointer mode, transposed V cache, wq Q4_K); -8 sum of squares / tail asked of the product library (PM_EXPERIMENTS only); -9 njobs outside 1..3

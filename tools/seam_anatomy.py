@@ -3,8 +3,10 @@
 Needs the measurement build of the library (s_memrealtime stamps inside the mat-vec and the single-token attention kernels,
 csrc/ts.hip):   python -m prima_cpp_amd.build ts -DPM_TS   then on the GPU box   PM355_LIB=ab/ts.so python tools/seam_anatomy.py
 
-Every workgroup's thread 0 records the chip-wide 100 MHz counter at: entry | after the rms-norm barrier | activations quantized in LDS |
-its wave finished its rows | all 16 waves finished | outputs stored. The tool replays the captured single-token graph a few times and
+Every workgroup's thread 0 records the chip-wide 100 MHz counter at: entry (first instruction of the kernel body, before any argument is touched) |
+after the rms-norm barrier | activations quantized in LDS | its wave finished its rows | all 16 waves finished | outputs stored - and, in the mat-vec,
+once the entry's loads (activation row, job 0's pre-issued weight steps) are out: the "entry" column = entry -> those loads issued, i.e. what the
+kernel does in front of its first memory traffic (part of "prologue"). The tool replays the captured single-token graph a few times and
 prints, per launch kind and averaged over the layers, the launch's span, how long its workgroups take to start, the prologue, the
 row phase, the spread of the finish times and the gap to the next launch's first workgroup (= the kernel boundary)."""
 import argparse
@@ -63,14 +65,15 @@ def main():
     t = buf.astype(np.int64)
     rows = []
     for s in range(used):
-        n = int(t[s, 0, 7])
+        n = int(t[s, 0, 7]) & 0xffffffff          # (upper half: ticks from entry to "entry's loads issued", mat-vec launches)
         if n <= 0:
             continue
         n = min(n, WGS)
         w = t[s, :n]
+        issued = (w[:, 7] >> 32) & 0xffffffff
         tag = int(w[0, 6])
         kind = "attention" if (tag & 15) == 2 else ("gate/up pair" if tag & 16 else f"matvec K={tag >> 12} x{(tag >> 8) & 3}")
-        rows.append(dict(slot=s, kind=kind, n=n, t0=w[:, 0], t1=w[:, 1], t2=w[:, 2], t3=w[:, 3], t4=w[:, 4], t5=w[:, 5]))
+        rows.append(dict(slot=s, kind=kind, n=n, issued=issued, t0=w[:, 0], t1=w[:, 1], t2=w[:, 2], t3=w[:, 3], t4=w[:, 4], t5=w[:, 5]))
     us = lambda ticks: float(ticks) / 100.0
     # name the launches by their place in the layer: QKV, attention, wo, gate/up, down
     names = ["QKV", "attention", "wo", "gate/up", "down"]
@@ -86,6 +89,7 @@ def main():
         d.append(dict(
             span=us(r["t5"].max() - r["t0"].min()),
             start_spread=us(r["t0"].max() - r["t0"].min()),
+            entry=us(r["issued"].mean()),
             prologue=us((r["t2"] - r["t0"]).mean()),
             norm=us((r["t1"] - r["t0"]).mean()) if r["t1"].max() > 0 else 0.0,
             rows_wave0=us((r["t3"] - r["t2"]).mean()),
@@ -96,7 +100,7 @@ def main():
             gap_next=us(nxt["t0"].min() - r["t5"].max()) if nxt else 0.0,
             stream_window=us(r["t4"].max() - r["t2"].min()),
         ))
-    cols = ["span", "start_spread", "prologue", "norm", "rows_all", "store", "end_spread", "gap_next", "stream_window"]
+    cols = ["span", "start_spread", "entry", "prologue", "norm", "rows_all", "store", "end_spread", "gap_next", "stream_window"]
     print(f"model {a.model}, {n_l} layers, position {a.pos}; microseconds, mean over the layers (s_memrealtime, 10 ns ticks)")
     print(f"{'launch':12s} {'n':>4s} " + " ".join(f"{c:>13s}" for c in cols))
     tot = 0.0
