@@ -382,6 +382,10 @@ PM355_API int pm355_attn_cached_long(const float * q_rot, void * k_cache, void *
 /* 0 when pm355_attn_cached_long serves the shape (head_dim 64 / 128, <= 16 KV heads, <= 16 query heads per KV head, n_ctx % 8 == 0); callers
  * keep pm355_attn_token's split form otherwise (e.g. MHA models with 32 / 40 KV heads). No device work. */
 PM355_API int pm355_attn_cached_long_check(int n_head, int n_head_kv, int head_dim, int n_ctx);
+/* Read-only: where the long-context forms keep their data inside the scratch, in floats (host arithmetic, no device work; tests/test_attn_batch_host.py).
+ * out[0..8) = spans of 128 keys over n_ctx | offsets of M, L, P | first ticket word of attn_flash.hip (n_head_kv words) | of attn_flash_mfma.hip
+ * (32 words) | the Q8_0 path's query rows (n_head * head_dim floats) | total. n_out >= 8, else PM355_E_SHAPE. */
+PM355_API int pm355_attn_long_scratch_layout(int n_head, int n_head_kv, int head_dim, int n_ctx, int64_t * out, int n_out);
 /* p[0] = a, p[1] = b on the stream (values travel as kernel arguments: no host buffer lifetime to manage) */
 PM355_API int pm355_set_i32x2(int32_t * d_p, int32_t a, int32_t b, pm355_stream_t stream);
 /* greedy sampler (src/llama-sampling.cpp:390-397): index of the first maximum */
@@ -500,6 +504,10 @@ PM355_API int pm355_small_batch_max_tokens(void);
 /* 0, or an error once a persistent decode kernel's device-wide barrier timed out (results since then are invalid; set
  * PM355_PERSISTENT=0 to use the 5-launches-per-layer path). Synchronizes the device. */
 PM355_API int pm355_model_check(pm355_model * m);
+/* Read-only: how many layer passes of multi-token windows (2 tokens and more) each attention form has served since the model was created -
+ * out[1] the matrix-core kernel with f32 rows, out[2] with F16 rows (the F16 prompt path), out[3] one workgroup per (head, token) over cached cells
+ * (pm355_attn_cached's kernel), out[4] pm355_attn_decode's kernel; out[0] unused. n_out >= 5, else PM355_E_SHAPE. Host counters, no device work. */
+PM355_API int pm355_model_attn_forms(const pm355_model * m, int64_t * out, int n_out);
 PM355_API int pm355_model_generate(pm355_model * m, int32_t * d_tokens_io, int pos0, int n_steps, int use_graph,
                                    pm355_stream_t stream);
 /* single-token step with the position held in device memory (graph-replayable building block of the piped ring):

@@ -15,6 +15,7 @@
 //   * more cells (up to the long-context threshold): the per-head body of attn_device.h in its CACHED form.
 #include "attn_device.h"
 #include "attn_tail_device.h"
+#include "pm355_kernels.h"
 #include "pm355_layer_ops.h"
 
 namespace {
@@ -160,7 +161,7 @@ int pm_launch_attn_cached(const pm_attn_tok & t, hipStream_t st) {
     const int32_t * pos0 = t.pos ? t.pos : t.dyn;   // ggml-graph mode: cells come from dyn; keep every pointer the kernel may touch valid
     if (!pos0) return -1;
     auto launch = [&](auto kern) {
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        pm_allow_big_lds((const void *) kern, lds);
         AttnP a = {t.q, nullptr, nullptr, (uint16_t *) t.kc, (uint16_t *) t.vc, pos0, t.seq, t.seq_stride, nullptr, t.out, t.H, t.Hkv, t.n_ctx, t.scale,
                    RopeP{}, t.dyn, (const float *) t.mask, t.mask_f16, pm_ts_next_slot()};
         hipLaunchKernelGGL(kern, dim3(t.H, t.n_tok), dim3(256), lds, st, a);

@@ -24,7 +24,7 @@
 
 namespace {
 
-constexpr int CK = 128;                          // keys per chunk (one pass of the workgroup)
+constexpr int CK = PM_FLASH_CK;                  // keys per chunk (one pass of the workgroup)
 constexpr int RMAX = 8;
 
 struct FlashP {
@@ -328,23 +328,14 @@ __global__ __launch_bounds__(256) void attn_flash_kernel(FlashP p) {
 
 } // namespace
 
-// scratch floats: M, L [H][nspan_max], P [nspan_max][H][dh], tickets [Hkv] (the caller zeroes the scratch once after allocating it)
-size_t pm_attn_flash_scratch_floats(int H, int Hkv, int dh, int n_ctx) {
-    const size_t nspan = (size_t) (n_ctx + CK - 1) / CK;
-    return 2 * (size_t) H * nspan + nspan * H * dh + (size_t) Hkv + 64 + 64 + (size_t) H * dh;      // (+ the Q8_0 path's query rows: pm_attn_flash_qrot_offset)
-}
-size_t pm_attn_flash_qrot_offset(int H, int Hkv, int dh, int n_ctx) {
-    const size_t nspan = (size_t) (n_ctx + CK - 1) / CK;
-    return 2 * (size_t) H * nspan + nspan * H * dh + (size_t) Hkv + 64 + 64;      // behind the tickets of both flash kernels (attn_flash_mfma.hip: + Hkv + 16 .. + 48)
-}
-
+// scratch: pm_attn_flash_layout (the caller zeroes it once after allocating it)
 // q, k, v = the RAW projections of the token; RoPE, KV store and attention over cells [0, n_kv) happen in this one launch.
 // max_cells bounds the cells attended (sizes the grid: spans beyond n_kv exit at once); 0 = n_ctx. -1: unsupported shape.
 int pm_launch_attn_flash(const pm_attn_tok & a, hipStream_t st) {
     const int H = a.H, Hkv = a.Hkv, dh = a.dh, n_ctx = a.n_ctx; float * const scratch = a.scratch;
     if ((dh != 64 && dh != 128) || H % Hkv || H / Hkv > RMAX || n_ctx % 8 || !scratch) return -1;
     if (!a.rope || a.k_q8 || a.v_q8 || a.n_tok != 1) return -1;
-    const int nspan_max = (n_ctx + CK - 1) / CK;
+    const pm_flash_scratch lay = pm_attn_flash_layout(H, Hkv, dh, n_ctx);
     const int cells = a.cells > 0 && a.cells < n_ctx ? a.cells : n_ctx;
     // span = keys per workgroup: 128 up to 8k cells, then grown so that a KV head never has more than 64 partials to merge
     int span = CK;
@@ -352,8 +343,8 @@ int pm_launch_attn_flash(const pm_attn_tok & a, hipStream_t st) {
     FlashP p = {};
     p.q = a.q; p.k = a.k; p.v = a.v; p.kc = (uint16_t *) a.kc; p.vc = (uint16_t *) a.vc; p.pos0_ptr = a.pos; p.seq_ptr = a.seq; p.seq_stride = a.seq_stride;
     p.ff = a.freq_factors; p.out = a.out;
-    p.M = scratch; p.L = p.M + (size_t) H * nspan_max; p.P = p.L + (size_t) H * nspan_max; p.ticket = (unsigned *) (p.P + (size_t) nspan_max * H * dh);
-    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nspan = nspan_max; p.span = span; p.scale = a.scale; p.r = rope_p(*a.rope);
+    p.M = scratch + lay.M; p.L = scratch + lay.L; p.P = scratch + lay.P; p.ticket = (unsigned *) (scratch + lay.tickets);
+    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nspan = lay.nspan; p.span = span; p.scale = a.scale; p.r = rope_p(*a.rope);
     p.dyn = a.dyn; p.mask = a.mask; p.mask_f16 = a.mask_f16; p.vm = a.v_rowmajor ? 1 : 0;
     const dim3 grid((cells + span - 1) / span, Hkv);
     if (dh == 128) {

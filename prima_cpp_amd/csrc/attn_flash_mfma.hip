@@ -386,7 +386,7 @@ __global__ __launch_bounds__(256, 2) void attn_flash_mfma_kernel(FlashM p) {
 
 } // namespace
 
-// q = rotated, F16-rounded query rows; the caches already hold this token (transposed V cache). scratch: pm_attn_flash_scratch_floats()
+// q = rotated, F16-rounded query rows; the caches already hold this token (transposed V cache). scratch: pm_attn_flash_layout,
 // zeroed once. -1: shape not served (head_dim 64 / 128, <= 16 query heads per KV head, n_ctx % 8 == 0).
 // Shapes the matrix-core kernel serves: head_dim 64 / 128, <= 16 query heads per KV head, n_ctx % 8 == 0, and <= 16 KV heads - the arrival
 // counters live at ticket[g] / ticket[16 + g] and the bounded spin of the merging workgroups assumes that the whole grid (n_head_kv x <= 64 spans
@@ -405,12 +405,11 @@ int pm_launch_attn_flash_cached(const pm_attn_tok & a, hipStream_t st) {
     if ((k_q8 || v_q8) && (!v_rowmajor || a.seq)) return -1;        // Q8_0 caches: flash-attention layout (row-major V), one sequence slab
     const int32_t * pos0 = a.pos ? a.pos : a.dyn;
     if (!pos0) return -1;
-    const int CK = 128;
-    const int nspan_max = (n_ctx + CK - 1) / CK;
+    const pm_flash_scratch lay = pm_attn_flash_layout(H, Hkv, dh, n_ctx);
     const int cells = a.cells > 0 && a.cells < n_ctx ? a.cells : n_ctx;
     // spans: 128 keys each until the KV heads together fill the CUs (256 workgroups: 32 spans per head at 8 KV heads - measured against 64
     // and 16 at 8k .. 32k cells), then longer spans; never more than 64 partials per head (the mergers' LDS tables)
-    int span = CK, parts = 256 / Hkv;
+    int span = PM_FLASH_CK, parts = 256 / Hkv;
     parts = parts < 16 ? 16 : parts > 64 ? 64 : parts;
     // (measurement only: PM355_FLASH_PARTS = spans per KV head, 1 .. 64 - profiles/r05_long_context_spans.txt)
     static const int parts_env = [] { const char * e = getenv("PM355_FLASH_PARTS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 64 ? v : 0; }();
@@ -418,8 +417,8 @@ int pm_launch_attn_flash_cached(const pm_attn_tok & a, hipStream_t st) {
     while ((cells + span - 1) / span > parts) span *= 2;
     FlashM p = {};
     p.q = a.q; p.kc = (const uint16_t *) a.kc; p.vc = (const uint16_t *) a.vc; p.pos0_ptr = pos0; p.seq_ptr = a.seq; p.seq_stride = a.seq_stride; p.out = a.out;
-    p.M = scratch; p.L = p.M + (size_t) H * nspan_max; p.P = p.L + (size_t) H * nspan_max; p.ticket = (unsigned *) (p.P + (size_t) nspan_max * H * dh) + Hkv + 16;    // (behind attn_flash.hip's tickets, which must read 0 between its launches)
-    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nspan = nspan_max; p.span = span; p.scale = a.scale;
+    p.M = scratch + lay.M; p.L = scratch + lay.L; p.P = scratch + lay.P; p.ticket = (unsigned *) (scratch + lay.tickets_mfma);
+    p.H = H; p.Hkv = Hkv; p.n_ctx = n_ctx; p.nspan = lay.nspan; p.span = span; p.scale = a.scale;
     p.dyn = a.dyn; p.mask = a.mask; p.mask_f16 = a.mask_f16; p.ts = pm_ts_next_slot();
     const dim3 grid(Hkv, (cells + span - 1) / span);
     if (k_q8 || v_q8) {

@@ -258,17 +258,16 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(PfP p) {
 
 } // namespace
 
-// n_ctx % 32 == 0 and head_dim 64 / 128 only (callers fall back to the per-token kernel otherwise)
-int pm_launch_attn_prefill(const float * q, const void * kc, const void * vc, const int32_t * pos0, const int32_t * seq,
-                           long seq_stride, float * out, int n_tok, int H, int Hkv, int dh, int n_ctx, float scale, hipStream_t st,
-                           const float * mask, long mask_stride, int n_kv, int v_rowmajor, int mask_f16, void * out_f16) {
-    if ((dh != 64 && dh != 128) || n_ctx % 32 || n_tok < 1) return -1;
-    if (mask && (n_kv < 1 || n_kv > n_ctx || n_kv % 4 || mask_stride % 4)) return -1;
-    if ((v_rowmajor || mask_f16) && !mask) return -1;                 // the flash-attention form exists in ggml-graph mode only
-    PfP p = {q, (const uint16_t *) kc, (const uint16_t *) vc, pos0, seq, seq_stride, out, n_tok, H, Hkv, n_ctx, scale, mask, mask_stride, n_kv,
-             v_rowmajor ? 1 : 0, mask_f16 ? 1 : 0, (_Float16 *) out_f16};
-    const dim3 grid((n_tok + 127) / 128, H);
-    if (dh == 128) hipLaunchKernelGGL(attn_prefill_kernel<128>, grid, dim3(256), 0, st, p);
+// n_ctx % 32 == 0 and head_dim 64 / 128 only (callers fall back to the per-token kernel otherwise); the modes: pm_attn_batch, pm355_layer_ops.h
+int pm_launch_attn_prefill(const pm_attn_batch & a, hipStream_t st) {
+    if ((a.dh != 64 && a.dh != 128) || a.n_ctx % 32 || a.n_tok < 1) return -1;
+    if (a.mask && (a.n_kv < 1 || a.n_kv > a.n_ctx || a.n_kv % 4 || a.mask_stride % 4)) return -1;
+    if ((a.v_rowmajor || a.mask_f16) && !a.mask) return -1;           // the flash-attention form exists in ggml-graph mode only
+    if (!a.out == !a.out_f16 || !a.pos == !a.mask || (a.seq && !a.pos)) return -1;      // one output, one mode: nothing given is dropped
+    PfP p = {a.q, (const uint16_t *) a.kc, (const uint16_t *) a.vc, a.pos, a.seq, a.seq_stride, a.out, a.n_tok, a.H, a.Hkv, a.n_ctx, a.scale,
+             (const float *) a.mask, a.mask_stride, a.n_kv, a.v_rowmajor ? 1 : 0, a.mask_f16 ? 1 : 0, (_Float16 *) a.out_f16};
+    const dim3 grid((a.n_tok + 127) / 128, a.H);
+    if (a.dh == 128) hipLaunchKernelGGL(attn_prefill_kernel<128>, grid, dim3(256), 0, st, p);
     else           hipLaunchKernelGGL(attn_prefill_kernel<64>, grid, dim3(256), 0, st, p);
     return 0;
 }

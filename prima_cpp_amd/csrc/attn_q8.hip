@@ -384,18 +384,6 @@ __global__ __launch_bounds__(DH) void q8_token_prep_kernel(Q8TokP a, float * q_o
     } else if (writer) ((uint16_t *) vdst)[tid] = f2h(xv);
 }
 
-// > 48 KiB of dynamic LDS needs the function attribute once per (kernel, device); the kernels here share their pointer TYPE, so the
-// bookkeeping is keyed on the pointer value
-void set_lds(const void * kern, size_t lds) {
-    if (lds <= 48 * 1024) return;
-    static const void * done[64][2] = {};
-    static int n_done = 0;
-    const void * dev = (const void *) (uintptr_t) (pm_cur_dev() + 1);
-    for (int i = 0; i < n_done; ++i) if (done[i][0] == kern && done[i][1] == dev) return;
-    (void) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (n_done < 64) { done[n_done][0] = kern; done[n_done][1] = dev; ++n_done; }
-}
-
 } // namespace
 
 // CPY f32 -> Q8_0 (dst = n/32 contiguous native blocks); -1: unsupported
@@ -420,7 +408,7 @@ int pm_launch_flash_attn_ext_q8(const pm355_tensor * q, const pm355_tensor * k, 
     if (softcap != 0.0f) scale /= softcap;
     const dim3 grid((unsigned) q->ne[1], (unsigned) q->ne[2], (unsigned) q->ne[3]);
     auto go = [&](auto kern) {
-        set_lds((const void *) kern, lds);
+        pm_allow_big_lds((const void *) kern, lds);
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, to_tdq(q), to_tdq(k), to_tdq(v), mask ? (const char *) mask->data : nullptr,
                            mask ? (long) mask->nb[1] : 0, to_tdq(dst), scale, softcap);
     };
@@ -458,7 +446,7 @@ int pm_launch_attn_q8_token(const pm_attn_tok & t, hipStream_t st) {
     Q8TokP a;
     a.q = t.q; a.k = t.k; a.v = t.v; a.kc = (uint8_t *) t.kc; a.vc = (uint8_t *) t.vc; a.pos = t.pos; a.dyn = t.dyn; a.mask = t.mask; a.mask_f16 = t.mask_f16;
     a.ff = t.freq_factors; a.out = t.out; a.H = H; a.Hkv = t.Hkv; a.n_ctx = t.n_ctx; a.scale = t.scale; a.r = rope_p(*t.rope);
-    auto go = [&](auto kern) { set_lds((const void *) kern, lds); hipLaunchKernelGGL(kern, dim3(H), dim3(256), lds, st, a); };
+    auto go = [&](auto kern) { pm_allow_big_lds((const void *) kern, lds); hipLaunchKernelGGL(kern, dim3(H), dim3(256), lds, st, a); };
     if (dh == 128) {
         if (k_q8 && v_q8) go(attn_q8_token_kernel<128, true, true>); else if (k_q8) go(attn_q8_token_kernel<128, true, false>); else go(attn_q8_token_kernel<128, false, true>);
     } else {

@@ -375,7 +375,11 @@ int pm355_rope_kv_store(const float * q, const float * k, const float * v, float
                         void * kc, void * vc, const int32_t * d_pos0, const float * ff, int n_tokens, int H, int Hkv, int dh,
                         int n_ctx, const pm355_rope_params * rp, pm355_stream_t st) {
     if (!rp || rp->n_dims % 2 || rp->n_dims > dh || dh % 2) return fail(PM355_E_SHAPE, "rope: n_dims");
-    pm_launch_rope_kv_store(q, k, v, q_out, k_out_f32, kc, vc, d_pos0, nullptr, 0, ff, n_tokens, H, Hkv, dh, n_ctx, pm_rope_cfg_of(*rp), S(st));
+    const pm_rope_cfg c = pm_rope_cfg_of(*rp);
+    pm_rope_store r = {};
+    r.q = q; r.k = k; r.v = v; r.q_out = q_out; r.k_out_f32 = k_out_f32; r.kc = kc; r.vc = vc; r.pos = d_pos0; r.freq_factors = ff;
+    r.n_tok = n_tokens; r.H = H; r.Hkv = Hkv; r.dh = dh; r.n_ctx = n_ctx; r.rope = &c;
+    pm_launch_rope_kv_store(r, S(st));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -388,9 +392,12 @@ int pm355_attn_decode(const float * q, const void * kc, const void * vc, const i
     HIP_TRY(hipGetLastError());
     return 0;
 }
-size_t pm355_attn_split_scratch_floats(int H, int dh, int n_ctx) {       // (covers both long-context forms: attn_split.hip and attn_flash.hip)
-    const size_t a = pm_attn_split_scratch_floats(H, dh, n_ctx), b = pm_attn_flash_scratch_floats(H, H, dh, n_ctx);
-    return a > b ? a : b;
+size_t pm355_attn_split_scratch_floats(int H, int dh, int n_ctx) { return pm_attn_long_scratch_floats(H, H, dh, n_ctx); }     // (every long-context form; no n_head_kv here: n_head is the upper bound)
+int pm355_attn_long_scratch_layout(int H, int Hkv, int dh, int n_ctx, int64_t * out, int n_out) {
+    if (!out || n_out < 8 || H < 1 || Hkv < 1 || dh < 1 || n_ctx < 1) return fail(PM355_E_SHAPE, "attn_long_scratch_layout: arguments");
+    const pm_flash_scratch s = pm_attn_flash_layout(H, Hkv, dh, n_ctx);
+    const int64_t v[8] = {s.nspan, (int64_t) s.M, (int64_t) s.L, (int64_t) s.P, (int64_t) s.tickets, (int64_t) s.tickets_mfma, (int64_t) s.qrot, (int64_t) s.total};
+    memcpy(out, v, sizeof v); return 0;
 }
 int pm355_attn_decode_split(const float * q_rot, const void * kc, const void * vc, const int32_t * d_pos0, float * out, float * scratch,
                             int H, int Hkv, int dh, int n_ctx, float kq_scale, pm355_stream_t st) {
@@ -404,17 +411,23 @@ int pm355_attn_decode_split(const float * q_rot, const void * kc, const void * v
 }
 int pm355_attn_prefill(const float * q, const void * kc, const void * vc, const int32_t * d_pos0, float * out, int n_tokens,
                        int H, int Hkv, int dh, int n_ctx, float kq_scale, pm355_stream_t st) {
-    if (pm_launch_attn_prefill(q, kc, vc, d_pos0, nullptr, 0, out, n_tokens, H, Hkv, dh, n_ctx, kq_scale, S(st)))
-        return fail(PM355_E_RANGE, "attn_prefill: head_dim must be 64 or 128 and n_ctx a multiple of 32");
+    pm_attn_batch a = {};
+    a.q = q; a.kc = kc; a.vc = vc; a.pos = d_pos0; a.out = out; a.n_tok = n_tokens; a.H = H; a.Hkv = Hkv; a.dh = dh; a.n_ctx = n_ctx; a.scale = kq_scale;
+    if (pm_launch_attn_prefill(a, S(st)))
+        return !d_pos0 || !out ? fail(PM355_E_SHAPE, "attn_prefill: null pointer")
+                               : fail(PM355_E_RANGE, "attn_prefill: head_dim must be 64 or 128 and n_ctx a multiple of 32");
     HIP_TRY(hipGetLastError());
     return 0;
 }
 int pm355_attn_prefill_masked_ex(const float * q, const void * kc, const void * vc, const void * mask, int64_t mask_stride, float * out,
                                  int n_tokens, int H, int Hkv, int dh, int n_ctx, int n_kv, float kq_scale, int flags, pm355_stream_t st) {
     if (!mask) return fail(PM355_E_SHAPE, "attn_prefill_masked: mask required");
-    if (pm_launch_attn_prefill(q, kc, vc, nullptr, nullptr, 0, out, n_tokens, H, Hkv, dh, n_ctx, kq_scale, S(st), (const float *) mask, (long) mask_stride, n_kv,
-                               flags & PM355_ATTN_V_ROWMAJOR, flags & PM355_ATTN_MASK_F16))
-        return fail(PM355_E_RANGE, "attn_prefill_masked: head_dim 64/128, n_ctx % 32 == 0, n_kv % 4 == 0 <= n_ctx required");
+    pm_attn_batch a = {};
+    a.q = q; a.kc = kc; a.vc = vc; a.mask = mask; a.mask_stride = (long) mask_stride; a.n_kv = n_kv; a.out = out; a.n_tok = n_tokens; a.H = H; a.Hkv = Hkv;
+    a.dh = dh; a.n_ctx = n_ctx; a.scale = kq_scale; a.v_rowmajor = flags & PM355_ATTN_V_ROWMAJOR; a.mask_f16 = flags & PM355_ATTN_MASK_F16;
+    if (pm_launch_attn_prefill(a, S(st)))
+        return !out ? fail(PM355_E_SHAPE, "attn_prefill_masked: null pointer")
+                    : fail(PM355_E_RANGE, "attn_prefill_masked: head_dim 64/128, n_ctx % 32 == 0, n_kv % 4 == 0 <= n_ctx required");
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -583,7 +596,7 @@ int pm355_attn_token(const pm355_attn_token_args * a, const pm355_rope_params * 
             // (attn_flash_mfma.hip); max_keys = cells the grid is sized for, scratch zeroed once after its allocation
             if (!a->scratch) return fail(PM355_E_SHAPE, "attn_token(q8_0, long): scratch");
             pm_attn_tok prep = t, cached = t;
-            prep.out = a->scratch + pm_attn_flash_qrot_offset(a->n_head, a->n_head_kv, a->head_dim, a->n_ctx);
+            prep.out = a->scratch + pm_attn_flash_layout(a->n_head, a->n_head_kv, a->head_dim, a->n_ctx).qrot;
             cached.q = prep.out; cached.k = cached.v = nullptr; cached.pos = nullptr; cached.freq_factors = nullptr; cached.rope = nullptr;
             if (pm_launch_q8_token_prep(prep, S(st)) || pm_launch_attn_flash_cached(cached, S(st)))
                 return fail(PM355_E_UNSUPPORTED, "attn_token(q8_0, long): head_dim 64/128, <= 16 query heads per KV head, <= 16 KV heads, n_ctx % 8 == 0");

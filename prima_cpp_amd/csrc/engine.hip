@@ -38,6 +38,7 @@ struct pm355_model {
     Tensor tok_embd, out_norm, output, rope_freqs;
     int max_tokens = 0;
     bool finalized = false;
+    int64_t attn_ran[5] = {};             // layers of multi-token windows served by each AttnForm so far (attend(); pm355_model_attn_forms)
     pm_rope_cfg rope;
     // scratch (device)
     float * x = nullptr, * x1 = nullptr, * q = nullptr, * k = nullptr, * v = nullptr, * att = nullptr, * h = nullptr;
@@ -384,6 +385,51 @@ pm_attn_tok attn_args(const pm355_model * m, const Layer & L, int n_tok, long se
     a.H = hp.n_head; a.Hkv = hp.n_head_kv; a.dh = hp.head_dim; a.n_ctx = hp.n_ctx; a.scale = 1.0f / sqrtf((float) hp.head_dim);
     return a;
 }
+// the same for the multi-token matrix-core kernel (attn_prefill.hip): f32 rows into m->att, or F16 rows there for the wo GEMM
+pm_attn_batch attn_batch_args(const pm355_model * m, const Layer & L, int n_tok, long seq_stride, bool out_f16) {
+    const pm355_hparams & hp = m->hp;
+    pm_attn_batch a = {};
+    a.q = m->q; a.kc = L.kc; a.vc = L.vc; a.pos = m->d_pos; a.seq = m->d_ctl; a.seq_stride = seq_stride; a.n_tok = n_tok;
+    if (out_f16) a.out_f16 = m->att; else a.out = m->att;
+    a.H = hp.n_head; a.Hkv = hp.n_head_kv; a.dh = hp.head_dim; a.n_ctx = hp.n_ctx; a.scale = 1.0f / sqrtf((float) hp.head_dim);
+    return a;
+}
+// The attention of a multi-token layer path: its kernels in the order they are tried - the first that serves the shape runs - and what they need of the RoPE + KV-store
+// launch in front. attn_cached reads query rows ALREADY rounded to F16 (the decode kernel, fed by the wq | wk | wv epilogue, which rounds): only the small path stores them so
+// (round_q, and its epilogue), so the prompt paths may not fall back to it. attn_decode rounds q itself: either (the same bits, tests/test_gpu_ops.py::test_small_batch_attention_fallback_...)
+enum AttnForm { ATTN_NONE = 0, ATTN_MFMA, ATTN_MFMA_F16 /*F16 rows for the wo GEMM*/, ATTN_CACHED, ATTN_DECODE };
+struct AttnChain { bool round_q; int mfma_min /*tokens from which the matrix-core kernel is tried*/; AttnForm form[3]; };
+const AttnChain ATTN_PROMPT_I8  = {false, 1, {ATTN_MFMA, ATTN_DECODE, ATTN_NONE}};
+const AttnChain ATTN_PROMPT_F16 = {false, 1, {ATTN_MFMA_F16, ATTN_DECODE, ATTN_NONE}};       // (falls back to f32 rows: the caller switches the wo activations)
+// one workgroup per (head, token) below SMALL_ATTN_MFMA_MIN tokens (attn_cached.hip: 11 -> ~4 us per layer at 2..8 tokens), from there on the prompt path's kernel
+// (12 us per layer at 32 tokens against 26 for 2048 small workgroups); a shape attn_cached refuses (head_dim, scores beyond 150 KiB of LDS) ends at attn_decode
+const AttnChain ATTN_SMALL      = {true, SMALL_ATTN_MFMA_MIN, {ATTN_MFMA, ATTN_CACHED, ATTN_DECODE}};
+// RoPE + KV store of T tokens (q rotated in place) unless the wq | wk | wv epilogue did them, then their attention over layer L's cells into m->att: the form that ran
+AttnForm attend(pm355_model * m, const Layer & L, int T, bool rope_done, const AttnChain & c, hipStream_t st) {
+    const pm355_hparams & hp = m->hp;
+    const long kv_stride = (long) hp.n_ctx * hp.n_head_kv * hp.head_dim;
+    if (!rope_done) {
+        pm_rope_store r = {};
+        r.q = m->q; r.k = m->k; r.v = m->v; r.q_out = m->q; r.kc = L.kc; r.vc = L.vc; r.pos = m->d_pos; r.seq = m->d_ctl; r.seq_stride = kv_stride;
+        r.freq_factors = (const float *) m->rope_freqs.d;
+        r.n_tok = T; r.H = hp.n_head; r.Hkv = hp.n_head_kv; r.dh = hp.head_dim; r.n_ctx = hp.n_ctx; r.rope = &m->rope; r.round_q = c.round_q;
+        pm_launch_rope_kv_store(r, st);
+    }
+    const pm_attn_tok at = attn_args(m, L, T, kv_stride);
+    for (const AttnForm f : c.form) {
+        int rc = -1;
+        switch (f) {
+        case ATTN_MFMA: case ATTN_MFMA_F16:
+            if (T >= c.mfma_min) rc = pm_launch_attn_prefill(attn_batch_args(m, L, T, kv_stride, f == ATTN_MFMA_F16), st);
+            break;
+        case ATTN_CACHED: rc = pm_launch_attn_cached(at, st); break;
+        case ATTN_DECODE: rc = pm_launch_attn_decode(at, st); break;
+        case ATTN_NONE: break;
+        }
+        if (rc == 0) { ++m->attn_ran[f]; return f; }
+    }
+    return ATTN_NONE;
+}
 
 // The single-token layer stack as ONE persistent launch: the same launches run_layers_fused issues, appended as phases (decode_engine.hip).
 // nullptr: this window is not served (types, shapes, streaming, long-context regime) - the caller takes the five-launch path.
@@ -617,8 +663,7 @@ int gemm1(const Tensor & w, pm_gemm_acts x, float * y, void * yh, const float * 
 // prompts on the integer matrix cores over Q8_K activations (PM355_PROMPT_I8=1, mmq_big.hip)
 int layer_prompt_i8(pm355_model * m, const Layer & L, int T, const float * cur, float * x_mid, float * x_next, hipStream_t st) {
     const pm355_hparams & hp = m->hp;
-    const int E = hp.n_embd, H = hp.n_head, Hkv = hp.n_head_kv, dh = hp.head_dim, F = hp.n_ff;
-    const float kq_scale = 1.0f / sqrtf((float) dh);
+    const int E = hp.n_embd, Eq = hp.n_head * hp.head_dim, F = hp.n_ff;
     auto TB = [&](int K) { return pm_q8k_tables_at(m->tab_big, K); };
     auto GI = [&](const Tensor & w, float * y, const float * bias, const float * resid, hipStream_t s2 = nullptr) {
         return pm_launch_mmq_big(w.type, w.d, m->aq_k, m->tab_big, y, (int) w.K, (int) w.N, T, bias, resid, s2 ? s2 : st);
@@ -639,13 +684,8 @@ int layer_prompt_i8(pm355_model * m, const Layer & L, int T, const float * cur, 
     (void) hipEventRecord(m->side_b, m->side);
     (void) hipStreamWaitEvent(st, m->side_b, 0);
     if (rc) return seterr(m, PM355_E_UNSUPPORTED, "prefill: qkv mat-mul (integer matrix cores)");
-    const long kvs = (long) hp.n_ctx * Hkv * dh;
-    pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kvs,
-                            (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st);
-    if (pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st) &&
-        pm_launch_attn_decode(attn_args(m, L, T, kvs), st))
-        return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
-    pm_launch_quantize_q8k(m->att, m->aq_k, H * dh, T, st, TB(H * dh));
+    if (attend(m, L, T, false, ATTN_PROMPT_I8, st) == ATTN_NONE) return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
+    pm_launch_quantize_q8k(m->att, m->aq_k, Eq, T, st, TB(Eq));
     if (GI(L.t[PM355_T_WO], x_mid, nullptr, cur)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: wo mat-mul");
     pm_launch_rmsnorm_q8k(x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, nullptr, m->aq_k, E, T, hp.rms_eps, st, nullptr, TB(E));
     if (GI(L.t[PM355_T_FFN_GATE], m->h, nullptr, nullptr) || GI(L.t[PM355_T_FFN_UP], m->h2, nullptr, nullptr))
@@ -658,8 +698,7 @@ int layer_prompt_i8(pm355_model * m, const Layer & L, int T, const float * cur, 
 // the engine's scratch - xn / att in place of their f32 forms, h = silu(gate) * up into h2: no conversion launches, half the bytes
 int layer_prompt_f16(pm355_model * m, const Layer & L, int T, const float * cur, float * x_mid, float * x_next, hipStream_t st) {
     const pm355_hparams & hp = m->hp;
-    const int E = hp.n_embd, H = hp.n_head, Hkv = hp.n_head_kv, dh = hp.head_dim;
-    const float kq_scale = 1.0f / sqrtf((float) dh);
+    const int E = hp.n_embd;
     const pm_gemm_acts xn = {nullptr, m->xn};
     pm_launch_rmsnorm_q8k(cur, (const float *) L.t[PM355_T_ATTN_NORM].d, nullptr, nullptr, E, T, hp.rms_eps, st, m->xn);
     // wq | wk | wv: ONE launch over the shared activations, each matrix with its own quant type (mmq_pf.hip jobs; wk / wv alone - N = n_head_kv * head_dim -
@@ -668,14 +707,9 @@ int layer_prompt_f16(pm355_model * m, const Layer & L, int T, const float * cur,
                                 gemm_job(L.t[PM355_T_WK], m->k, nullptr, (const float *) L.t[PM355_T_BK].d, nullptr),
                                 gemm_job(L.t[PM355_T_WV], m->v, nullptr, (const float *) L.t[PM355_T_BV].d, nullptr)};
     if (pm_launch_gemm(qkv, 3, xn, E, T, 0, st)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: qkv gemm");
-    const long kvs = (long) hp.n_ctx * Hkv * dh;
-    pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kvs,
-                            (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st);
-    pm_gemm_acts att = {nullptr, m->att};                        // the prefill attention kernel writes F16, the decode kernel f32
-    if (pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kvs, nullptr, T, H, Hkv, dh, hp.n_ctx, kq_scale, st, nullptr, 0, 0, 0, 0, m->att)) {
-        att = {m->att, nullptr};
-        if (pm_launch_attn_decode(attn_args(m, L, T, kvs), st)) return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
-    }
+    const AttnForm af = attend(m, L, T, false, ATTN_PROMPT_F16, st);
+    if (af == ATTN_NONE) return seterr(m, PM355_E_RANGE, "prefill: n_ctx too large for the attention kernel");
+    const pm_gemm_acts att = af == ATTN_MFMA_F16 ? pm_gemm_acts{nullptr, m->att} : pm_gemm_acts{m->att, nullptr};      // the prefill attention kernel writes F16, the decode kernel f32
     if (gemm1(L.t[PM355_T_WO], att, x_mid, nullptr, nullptr, cur, T, st)) return seterr(m, PM355_E_UNSUPPORTED, "prefill: wo gemm");
     pm_launch_rmsnorm_q8k(x_mid, (const float *) L.t[PM355_T_FFN_NORM].d, nullptr, nullptr, E, T, hp.rms_eps, st, m->xn);
     // ffn_gate | ffn_up as ONE launch of pair tiles: h2 = F16(silu(gate) * up) comes out of the up waves' epilogue, the gate result crosses over inside
@@ -712,24 +746,9 @@ int small_qkv(pm355_model * m, const Layer & L, ActQ a, int T, bool small, bool 
 }
 // RoPE + KV store (unless the wq | wk | wv epilogue did them), attention, wo + residual -> x_mid
 int small_attention(pm355_model * m, const Layer & L, int T, bool rope_done, const float * cur, float * x_mid, hipStream_t st) {
-    const pm355_hparams & hp = m->hp;
-    const int H = hp.n_head, Hkv = hp.n_head_kv, dh = hp.head_dim;
-    const float kq_scale = 1.0f / sqrtf((float) dh);
-    const long kv_stride = (long) hp.n_ctx * Hkv * dh;
-    // q rotated AND rounded to F16, every token's K row / V column stored: the attention of a small batch then is the single-token kernel over
-    // cached cells, one workgroup per (head, token) (attn_cached.hip: one barrier up to 64 cells; 11 -> ~4 us per layer at 2..8 tokens)
-    if (!rope_done)
-        pm_launch_rope_kv_store(m->q, m->k, m->v, m->q, nullptr, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride,
-                                (const float *) m->rope_freqs.d, T, H, Hkv, dh, hp.n_ctx, m->rope, st, 1);
-    // (a shape attn_cached refuses - head_dim other than 64 / 128 / 256, scores beyond 150 KiB of LDS - falls back to attn_decode, which rounds q to
-    //  F16 itself: the pre-rounded rows give it the same bits as raw ones, tests/test_gpu_ops.py::test_small_batch_attention_fallback_...)
-    // (from SMALL_ATTN_MFMA_MIN tokens on: the prompt path's matrix-core kernel - 12 us per layer at 32 tokens against 26 for 2048 small workgroups)
-    const pm_attn_tok at = attn_args(m, L, T, kv_stride);
-    if (!(T >= SMALL_ATTN_MFMA_MIN && pm_launch_attn_prefill(m->q, L.kc, L.vc, m->d_pos, m->d_ctl, kv_stride, m->att, T, H, Hkv, dh, hp.n_ctx, kq_scale, st) == 0) &&
-        pm_launch_attn_cached(at, st) && pm_launch_attn_decode(at, st))
-        return seterr(m, PM355_E_RANGE, "decode: n_ctx too large for the decode-attention kernel");
+    if (attend(m, L, T, rope_done, ATTN_SMALL, st) == ATTN_NONE) return seterr(m, PM355_E_RANGE, "decode: n_ctx too large for the decode-attention kernel");
     const Tensor * wo[1] = {&L.t[PM355_T_WO]};
-    ActQ a = quantize_for(m, m->att, H * dh, T, wo, 1, st);
+    ActQ a = quantize_for(m, m->att, m->hp.n_head * m->hp.head_dim, T, wo, 1, st);
     return matmul_small(m, L.t[PM355_T_WO], a, T, x_mid, nullptr, cur, st) ? seterr(m, PM355_E_UNSUPPORTED, "decode: wo gemv") : 0;
 }
 // ffn_norm, ffn_gate | ffn_up, silu * mul, ffn_down + residual -> x_next
@@ -996,11 +1015,10 @@ int pm355_model_finalize_seqs(pm355_model * m, int max_tokens, int n_seq) {
     if (ok) (void) hipMemset(m->att_tk, 0, 65 * 4);
     if (ok && T > MMQ_MAX_TOKENS && !m->no_big) ok = A((void **) &m->tab_big, pm_mmq_big_table_bytes((int) ((maxK + 255) / 256 * 256), (int) T));
     if (!ok) return seterr(m, PM355_E_NOMEM, "finalize: scratch");
+    const size_t long_scratch_bytes = pm_attn_long_scratch_floats(hp.n_head, hp.n_head_kv, hp.head_dim, hp.n_ctx) * 4;
     if (hp.n_head / hp.n_head_kv <= 8 && (hp.head_dim == 64 || hp.head_dim == 128) &&
-        !A((void **) &m->split_scratch, std::max(pm_attn_split_scratch_floats(hp.n_head, hp.head_dim, hp.n_ctx),
-                                                 pm_attn_flash_scratch_floats(hp.n_head, hp.n_head_kv, hp.head_dim, hp.n_ctx)) * 4)) return seterr(m, PM355_E_NOMEM, "finalize: attention scratch");
-    if (m->split_scratch) (void) hipMemset(m->split_scratch, 0, std::max(pm_attn_split_scratch_floats(hp.n_head, hp.head_dim, hp.n_ctx),
-                                                                         pm_attn_flash_scratch_floats(hp.n_head, hp.n_head_kv, hp.head_dim, hp.n_ctx)) * 4);   // (the flash kernel's tickets start at 0)
+        !A((void **) &m->split_scratch, long_scratch_bytes)) return seterr(m, PM355_E_NOMEM, "finalize: attention scratch");
+    if (m->split_scratch) (void) hipMemset(m->split_scratch, 0, long_scratch_bytes);       // (the flash kernels' tickets start at 0)
     if (m->n_slots) {
         if (m->n_slots > m->hi - m->lo) m->n_slots = m->hi - m->lo;
         if (hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking) != hipSuccess) return seterr(m, PM355_E_HIP, "finalize: copy stream");
@@ -1196,6 +1214,11 @@ int pm355_model_check(pm355_model * m) {
         if (w) { snprintf(m->err, sizeof(m->err), "check: the decode engine's watchdog fired (code %d: 1 loader, 2 consumer barrier, 3 device-wide barrier, 4 item wait, 6 attention barrier)", w); return PM355_E_HIP; }
     }
 #endif
+    return 0;
+}
+int pm355_model_attn_forms(const pm355_model * m, int64_t * out, int n_out) {
+    if (!m || !out || n_out < 5) return PM355_E_SHAPE;
+    memcpy(out, m->attn_ran, sizeof m->attn_ran);
     return 0;
 }
 

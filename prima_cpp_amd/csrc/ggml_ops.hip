@@ -391,9 +391,7 @@ int pm355_op_soft_max(const pm355_tensor * a, const pm355_tensor * mask, const p
     const unsigned n_head = (unsigned) a->ne[2];
     const unsigned n_head_log2 = 1u << (unsigned) floor(log2((double) n_head));
     const float m0 = powf(2.0f, -(max_bias) / n_head_log2), m1 = powf(2.0f, -(max_bias / 2.0f) / n_head_log2);
-    static bool set[16] = {};
-    const int dv = lds > 48 * 1024 ? pm_cur_dev() : 0;
-    if (lds > 48 * 1024 && !set[dv]) { (void) hipFuncSetAttribute((const void *) soft_max_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); set[dv] = true; }
+    pm_allow_big_lds((const void *) soft_max_kernel, lds);
     (void) hipGetLastError();
     hipLaunchKernelGGL(soft_max_kernel, dim3((unsigned) rows), dim3(256), lds, S(st), to_td(a), mask ? (const char *) mask->data : nullptr,
                        mask ? mask->type : 0, mask ? (long) mask->nb[1] : 0, to_td(dst), scale, max_bias, m0, m1, n_head_log2);
@@ -426,9 +424,7 @@ int pm355_op_flash_attn_ext(const pm355_tensor * q, const pm355_tensor * k, cons
     const unsigned n_head = (unsigned) q->ne[2];
     const unsigned n_head_log2 = 1u << (unsigned) floor(log2((double) n_head));
     const float m0 = powf(2.0f, -(max_bias) / n_head_log2), m1 = powf(2.0f, -(max_bias / 2.0f) / n_head_log2);
-    static bool set[16] = {};
-    const int dv = lds > 48 * 1024 ? pm_cur_dev() : 0;
-    if (lds > 48 * 1024 && !set[dv]) { (void) hipFuncSetAttribute((const void *) flash_attn_ext_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); set[dv] = true; }
+    pm_allow_big_lds((const void *) flash_attn_ext_kernel, lds);
     (void) hipGetLastError();
     hipLaunchKernelGGL(flash_attn_ext_kernel, dim3((unsigned) q->ne[1], (unsigned) q->ne[2], (unsigned) q->ne[3]), dim3(256), lds, S(st),
                        to_td(q), to_td(k), to_td(v), mask ? (const char *) mask->data : nullptr, mask ? (long) mask->nb[1] : 0, to_td(dst),

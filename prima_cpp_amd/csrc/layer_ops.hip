@@ -327,23 +327,17 @@ pm_rope_cfg pm_rope_cfg_of(const pm355_rope_params & rp) {
     return c;
 }
 
-void pm_launch_rope_kv_store(const float * q, const float * k, const float * v, float * q_out, float * k_out_f32,
-                             void * kc, void * vc, const int32_t * pos0, const int32_t * seq, long seq_stride,
-                             const float * freq_factors,
-                             int n_tok, int H, int Hkv, int dh, int n_ctx, const pm_rope_cfg & c, hipStream_t st, int round_q) {
-    hipLaunchKernelGGL(rope_kv_store_kernel, dim3(H + Hkv, n_tok), dim3(64), 0, st,
-                       q, k, v, q_out, k_out_f32, (uint16_t *) kc, (uint16_t *) vc, pos0, seq, seq_stride, freq_factors, H, Hkv, dh, n_ctx, rope_p(c), round_q);
+void pm_launch_rope_kv_store(const pm_rope_store & a, hipStream_t st) {
+    hipLaunchKernelGGL(rope_kv_store_kernel, dim3(a.H + a.Hkv, a.n_tok), dim3(64), 0, st,
+                       a.q, a.k, a.v, a.q_out, a.k_out_f32, (uint16_t *) a.kc, (uint16_t *) a.vc, a.pos, a.seq, a.seq_stride, a.freq_factors,
+                       a.H, a.Hkv, a.dh, a.n_ctx, rope_p(*a.rope), a.round_q ? 1 : 0);
 }
 
 int pm_launch_attn_decode(const pm_attn_tok & a, hipStream_t st) {
     const int dh = a.dh, n_ctx = a.n_ctx;
     const size_t lds = (size_t) (dh + n_ctx) * 4;
     if (lds > PM_ATTN_LDS_MAX || dh % 8 || n_ctx % 8 || a.rope || a.dyn || a.mask || a.v_rowmajor || a.k_q8 || a.v_q8 || a.cells) return -1;
-    if (lds > 48 * 1024) {
-        static bool set[16] = {};
-        const int dv = pm_cur_dev();
-        if (!set[dv]) { (void) hipFuncSetAttribute((const void *) attn_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); set[dv] = true; }
-    }
+    pm_allow_big_lds((const void *) attn_decode_kernel, lds);
     hipLaunchKernelGGL(attn_decode_kernel, dim3(a.H, a.n_tok), dim3(256), lds, st,
                        a.q, (const uint16_t *) a.kc, (const uint16_t *) a.vc, a.pos, a.seq, a.seq_stride, a.out, a.H, a.Hkv, dh, n_ctx, a.scale);
     return 0;
@@ -355,7 +349,7 @@ int pm_launch_attn_rope_fused(const pm_attn_tok & t, hipStream_t st) {
     const size_t lds = pm_attn_head_lds(dh, t.n_ctx, t.v_rowmajor, t.cells);
     if (lds > PM_ATTN_LDS_MAX || !t.rope || t.k_q8 || t.v_q8 || t.n_tok != 1) return -1;
     auto launch = [&](auto kern) {
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        pm_allow_big_lds((const void *) kern, lds);
         AttnP a = {t.q, t.k, t.v, (uint16_t *) t.kc, (uint16_t *) t.vc, t.pos, t.seq, t.seq_stride, t.freq_factors, t.out, t.H, t.Hkv, t.n_ctx, t.scale,
                    rope_p(*t.rope), t.dyn, (const float *) t.mask, t.mask_f16, pm_ts_next_slot()};
         hipLaunchKernelGGL(kern, dim3(t.H), dim3(256), lds, st, a);

@@ -510,15 +510,6 @@ __global__ __launch_bounds__(PF_NTHR) void gemm_pf_kernel(PfP p) {
 
 template <int TA, int TB, int NT> constexpr size_t pf_lds_bytes() { return (size_t) 3 * NT * 32 * 128 + (size_t) 8 * (pf_wave_bytes<TA>() > pf_wave_bytes<TB>() ? pf_wave_bytes<TA>() : pf_wave_bytes<TB>()); }
 
-void pf_allow_lds(const void * kern, size_t lds) {
-    struct E { const void * k; int dev; };
-    static E done[64]; static int n_done = 0;
-    const int dev = pm_cur_dev();
-    for (int i = 0; i < n_done && i < 64; ++i) if (done[i].k == kern && done[i].dev == dev) return;
-    (void) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (n_done < 64) { done[n_done].k = kern; done[n_done].dev = dev; ++n_done; }
-}
-
 // split-K workspace of a (device, stream): 64 KiB of tile counters (zero between launches: the reducer resets its own) + the partial-tile slabs
 struct PfWs { hipStream_t st; int dev; uint8_t * p; size_t bytes; uint64_t use; };
 PfWs g_pf_ws[16] = {};
@@ -635,7 +626,7 @@ int pm_launch_gemm_pf_ex(const pm_gemm_job * jobs, int njobs, const void * xh, i
     }
     const int slots = full + split_slots * S;
     auto go = [&](auto kern, size_t lds) {
-        pf_allow_lds((const void *) kern, lds);
+        pm_allow_big_lds((const void *) kern, lds, 160 * 1024);
         hipLaunchKernelGGL(kern, dim3(8 * slots), dim3(PF_NTHR), lds, st, p);
     };
 #if PM_GEMM_ABLATE

@@ -15,16 +15,18 @@
 // through the plug-in: hipFuncSetAttribute and the CU count are per device, not per process)
 static inline int pm_cur_dev() { int d = 0; return (hipGetDevice(&d) == hipSuccess && d >= 0 && d < 16) ? d : 0; }
 
-// one-time hipFuncSetAttribute(MaxDynamicSharedMemorySize) per (kernel, device). Keyed on the kernel POINTER: a `static bool` inside a generic
-// lambda is shared by every instantiation that decays to the same function-pointer type, so only the first kernel launched would get it.
-static inline void pm_allow_big_lds(const void * kern, size_t lds) {
+// THE opt-in to more than 48 KiB of dynamic LDS, for every launcher of the product sources: one hipFuncSetAttribute(MaxDynamicSharedMemorySize, limit) per (kernel, device),
+// made by the first launch that needs it - later launches make no runtime call (none inside a stream capture either). Keyed on the kernel POINTER: a `static bool` inside a
+// generic lambda is shared by every instantiation that decays to the same function-pointer type, so only the first kernel launched would get it. No lock: the call is idempotent,
+// a lost race sets it twice. The table is one copy per translation unit (static inline): a kernel is launched only from the file that defines it, so no two copies hold one pointer.
+static inline void pm_allow_big_lds(const void * kern, size_t lds, size_t limit = 150 * 1024) {
     if (lds <= 48 * 1024) return;
     struct E { const void * k; int dev; };
     static E done[256]; static int n_done = 0;
     static hipError_t (*set)(const void *, hipFuncAttribute, int) = hipFuncSetAttribute;
     const int dev = pm_cur_dev();
     for (int i = 0; i < n_done && i < 256; ++i) if (done[i].k == kern && done[i].dev == dev) return;
-    (void) set(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);       // (idempotent: a lost race sets it twice)
+    (void) set(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) limit);
     if (n_done < 256) { done[n_done].k = kern; done[n_done].dev = dev; ++n_done; }
 }
 

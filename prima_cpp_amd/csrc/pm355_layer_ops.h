@@ -1,8 +1,10 @@
 // pm355_layer_ops.h — host launchers of the layer operations: layer_ops.hip, the attention forms (attn_cached / attn_split / attn_flash /
-// attn_flash_mfma / attn_prefill / attn_q8 .hip) and the RoPE configuration they share
+// attn_flash_mfma / attn_prefill / attn_q8 .hip) and the RoPE configuration they share. Argument blocks: pm_attn_tok (one token), pm_attn_batch (many tokens),
+// pm_rope_store (RoPE + KV store in front of them); pm_attn_flash_layout: the one layout of the long-context scratch
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include "../../include/prima_mi355.h"
 #include "pm355_types.h"
 
@@ -16,11 +18,15 @@ pm_rope_cfg pm_rope_cfg_of(const pm355_rope_params & rp);      // the C ABI's pa
 
 // type: one the embedding row lookup decodes (pm_embed_type_ok, pm355_types.h; pm355_get_rows and the engine's token embedding refuse the others)
 void pm_launch_embed(int type, const void * table, int K, const int32_t * tokens, int n_tok, float * out, hipStream_t st);
-void pm_launch_rope_kv_store(const float * q, const float * k, const float * v, float * q_out, float * k_out_f32,
-                             void * kc, void * vc, const int32_t * pos0, const int32_t * seq, long seq_stride,
-                             const float * freq_factors,
-                             int n_tok, int H, int Hkv, int dh, int n_ctx, const pm_rope_cfg & c, hipStream_t st,
-                             int round_q = 0);       // q_out rounded to F16 (what MUL_MAT(k, q) does to its src1): the form pm_launch_attn_cached reads
+// RoPE of n_tok tokens' raw q / k projections, their K rows / V columns stored in the F16 caches (transposed V); engine mode as below:
+// token t sits at position pos[seq ? *seq : 0] + t = its cell
+struct pm_rope_store {
+    const float * q, * k, * v; float * q_out, * k_out_f32;     // raw projections; rotated queries (may be q) and, optionally, the rotated keys in f32
+    void * kc, * vc; const int32_t * pos, * seq; long seq_stride; const float * freq_factors;
+    int n_tok, H, Hkv, dh, n_ctx; const pm_rope_cfg * rope;
+    bool round_q;                          // q_out rounded to F16 (what MUL_MAT(k, q) does to its src1): the form pm_launch_attn_cached reads
+};
+void pm_launch_rope_kv_store(const pm_rope_store & a, hipStream_t st);
 // ---- single-token attention: every form takes the same argument block -----------------------------------------------------------------
 // Engine mode: the token's position is pos[seq ? *seq : 0], its cache slab starts seq_stride elements per sequence further on, cell == position
 // and cells [0, pos] are attended. ggml-graph mode: dyn = device int32[2] {cache cell the token is stored in, cells attended}, the RoPE position
@@ -54,20 +60,47 @@ int  pm_launch_attn_cached(const pm_attn_tok & a, hipStream_t st);
 // updated; else q / k / v are the raw projections and rope + KV store happen inside the first kernel
 size_t pm_attn_split_scratch_floats(int H, int dh, int n_ctx);
 int  pm_launch_attn_split(const pm_attn_tok & a, hipStream_t st);
+// The scratch of the two one-launch long-context forms and of the Q8_0 path in front of the second, in floats.
+// Both kernels may run on one scratch in one process: each has ticket words of its own
+constexpr int PM_FLASH_CK = 128;           // keys per span of both kernels at their shortest: the partials are sized for ceil(n_ctx / CK) spans
+struct pm_flash_scratch {
+    int nspan;                             // rows of M / L / P: spans of PM_FLASH_CK keys over n_ctx (a launch that grows its spans uses fewer)
+    size_t M, L;                           // [H][nspan] each: running max / sum of exp of every (head, span)
+    size_t P;                              // [nspan][H][dh]: the spans' partial outputs
+    size_t tickets;                        // attn_flash.hip: Hkv arrival counters straight behind P; its last workgroup leaves them 0 for its next launch
+    size_t tickets_mfma;                   // attn_flash_mfma.hip: 32 words ([g], [16 + g], g < 16 KV heads) that count on from launch to launch, so never
+                                           // the other kernel's Hkv words, which must read 0: 16 words behind those, up to tickets + Hkv + 48
+    size_t qrot;                           // H * dh floats: the rotated (Q8_0 K cache: quantized) query rows pm_launch_q8_token_prep leaves for the cached
+                                           // kernel, Hkv + 64 + 64 words behind the first tickets: clear of the 48 above with a cache line to spare
+    size_t total;
+};
+inline pm_flash_scratch pm_attn_flash_layout(int H, int Hkv, int dh, int n_ctx) {
+    pm_flash_scratch s;
+    s.nspan = (n_ctx + PM_FLASH_CK - 1) / PM_FLASH_CK; s.M = 0; s.L = s.M + (size_t) H * s.nspan; s.P = s.L + (size_t) H * s.nspan;
+    s.tickets = s.P + (size_t) s.nspan * H * dh; s.tickets_mfma = s.tickets + Hkv + 16; s.qrot = s.tickets + Hkv + 64 + 64; s.total = s.qrot + (size_t) H * dh;
+    return s;
+}
+// floats of scratch that serve ANY long-context form (attn_split.hip included): what the engine or a C-ABI caller allocates and zeroes once (tickets start at 0)
+inline size_t pm_attn_long_scratch_floats(int H, int Hkv, int dh, int n_ctx) {
+    return std::max(pm_attn_split_scratch_floats(H, dh, n_ctx), pm_attn_flash_layout(H, Hkv, dh, n_ctx).total);
+}
 // long context in ONE launch (flash-decoding with an in-launch merge, attn_flash.hip); q / k / v raw projections
-size_t pm_attn_flash_scratch_floats(int H, int Hkv, int dh, int n_ctx);
 int  pm_launch_attn_flash(const pm_attn_tok & a, hipStream_t st);
 // long context over cached cells on the matrix cores (attn_flash_mfma.hip); F16 or Q8_0 caches
 int  pm_attn_flash_cached_ok(int H, int Hkv, int dh, int n_ctx);      // 0: served by the matrix-core long-context kernel
 int  pm_launch_attn_flash_cached(const pm_attn_tok & a, hipStream_t st);
-// where the long-context Q8_0 path parks the token's rotated (and, for a Q8_0 K cache, Q8_0-quantized) query rows inside the attention scratch
-size_t pm_attn_flash_qrot_offset(int H, int Hkv, int dh, int n_ctx);
-// causal multi-token attention on MFMA (attn_prefill.hip); -1: unsupported shape (head_dim 64/128, n_ctx % 32 == 0)
-int  pm_launch_attn_prefill(const float * q, const void * kc, const void * vc, const int32_t * pos0, const int32_t * seq,
-                            long seq_stride, float * out, int n_tok, int H, int Hkv, int dh, int n_ctx, float scale, hipStream_t st,
-                            const float * mask = nullptr, long mask_stride = 0, int n_kv = 0,   // mask != null: ggml-graph mode (cells [0, n_kv) + additive mask row per token)
-                            int v_rowmajor = 0, int mask_f16 = 0,                              // flash-attention graphs: row-major V cache, F16 mask rows
-                            void * out_f16 = nullptr);                                         // result as F16 (activations of the wo GEMM) instead of `out`
+// ---- multi-token attention over cached cells on MFMA (attn_prefill.hip) -----------------------------------------------------------------------
+// q = rotated query rows [n_tok][H * dh], the caches already hold the tokens. Engine mode (pos): token t attends cells [0, pos[seq ? *seq : 0] + t], causal.
+// ggml-graph mode (mask): cells [0, n_kv) plus the additive mask row of each token (mask_stride elements apart; f32, or F16 with mask_f16).
+// The rule above holds: -1 for a shape it does not serve (head_dim 64 / 128, n_ctx % 32 == 0, n_tok >= 1; with a mask n_kv in 1 .. n_ctx, n_kv % 4 == 0,
+// mask_stride % 4 == 0) and for a mode it does not serve: exactly one of out / out_f16, exactly one of pos / mask, seq only with pos, v_rowmajor and
+// mask_f16 (the flash-attention graphs) only with a mask.
+struct pm_attn_batch {
+    const float * q; const void * kc, * vc; const int32_t * pos, * seq; long seq_stride; const void * mask; long mask_stride; int n_kv;
+    float * out; void * out_f16;           // the result as f32, or as F16 (the activations of the wo GEMM)
+    int n_tok, H, Hkv, dh, n_ctx; float scale; bool v_rowmajor, mask_f16;
+};
+int  pm_launch_attn_prefill(const pm_attn_batch & a, hipStream_t st);
 // the per-token cos / sin table the QKV epilogue reads (tab[2 i], tab[2 i + 1] for rotation pair i; position = pos[seq ? *seq : 0])
 void pm_launch_rope_table(const pm_rope_cfg & c, const int32_t * pos, const int32_t * seq, const float * freq_factors, float * tab, hipStream_t st,
                           int n_tok = 1);    // n_tok > 1: tables of the tokens pos .. pos + n_tok - 1, n_dims floats each

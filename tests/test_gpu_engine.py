@@ -620,3 +620,59 @@ def test_single_token_decode_with_three_types_in_wq_wk_wv_vs_oracle(E, oracle):
         assert _nmse(a, b) < 1e-6
     oracle.model_free(ho)
     w.close()
+
+
+# (path, prompt tokens, model, the two windows, NMSE bound). n_ctx 64 / 160: a multiple of 32, the matrix-core kernel (attn_prefill.hip) serves it where the
+# path asks for it. n_ctx 72 / 136: a multiple of 8 only - that kernel refuses and the path's chain goes on (engine.hip: ATTN_SMALL, ATTN_PROMPT_F16, ATTN_PROMPT_I8)
+# The forms are the indices of pm355_model_attn_forms: 1 matrix-core kernel (f32 rows), 2 the same with F16 rows, 3 attn_cached, 4 attn_decode
+_CHAIN_CASES = [
+    ("small-5", 5, dict(n_layer=2, n_embd=256, n_head=4, n_head_kv=2, n_ff=512), (64, 72), (3, 3), 1e-3),        # below SMALL_ATTN_MFMA_MIN: attn_cached in both windows
+    # (n_embd 512: at 256 the small-batch mat-mul does not serve the layer and 20 tokens take the F16 prompt path - the count below told)
+    ("small-20", 20, dict(n_layer=2, n_embd=512, n_head=4, n_head_kv=2, n_ff=1024), (64, 72), (1, 3), 2e-3),     # matrix-core kernel at 64, attn_cached at 72
+    ("prompt-f16-40", 40, dict(n_layer=2, n_embd=512, n_head=4, n_head_kv=2, n_ff=1024), (64, 72), (2, 4), 2e-3),  # F16 rows at 64; at 72 attn_decode's f32 rows feed the wo GEMM
+    ("prompt-i8-128", 128, dict(n_layer=1, n_embd=1024, n_head=8, n_head_kv=2, n_ff=1024), (160, 136), (1, 4), 2e-3),   # PM355_PROMPT_I8=1: f32 rows (the F16 prompt path would count form 2); attn_decode at 136
+]
+
+
+def _attn_forms(w):
+    """pm355_model_attn_forms: layer passes of multi-token windows per attention form; None on a library in front of that entry (A/B runs)"""
+    import ctypes as C
+    if not hasattr(w.lib, "pm355_model_attn_forms"):
+        return None
+    f = w.lib.pm355_model_attn_forms
+    f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int]
+    out = (C.c_int64 * 5)()
+    assert f(w.h, out, 5) == 0
+    return list(out)
+
+
+@pytest.mark.parametrize("name,n_tok,shape,windows,forms,bound", _CHAIN_CASES, ids=[c[0] for c in _CHAIN_CASES])
+def test_multi_token_attention_chain_with_and_without_the_matrix_core_kernel(E, oracle, monkeypatch, name, n_tok, shape, windows, forms, bound):
+    """The attention of the three multi-token layer paths (engine.hip attend()) where its first kernel serves the window and where it refuses (n_ctx % 32 != 0)
+    and the next form of the path's chain runs: the prompt, then one single-token step from the cache the prompt wrote, against the oracle; the engine's
+    own count says that every layer of the prompt took the form the case is about and no other (the single token does not pass through attend()). Bounds: the
+    project's own for these token counts - NMSE 1e-3 (test_window_prefill_and_decode_vs_oracle) at 5 tokens, 2e-3 (test_prefill_mfma_path_vs_oracle,
+    test_prompt_f16_layer_on_the_third_generation_gemm_vs_oracle) at 20, 40 and 128."""
+    torch = E.torch
+    if name.startswith("prompt-i8"):
+        monkeypatch.setenv("PM355_PROMPT_I8", "1")
+    for n_ctx, form in zip(windows, forms):
+        rng = np.random.default_rng(131)
+        d = tiny_model(rng, arch=0, n_vocab=320, n_ctx=n_ctx, rope_freqs=True, quantize=_quantizer(), **shape)
+        w = E.Window(_hp(d), n_ctx=n_ctx)
+        w.load_desc(d)
+        w.finalize(max_tokens=n_tok)
+        ho = oracle.model_new(d)
+        toks = rng.integers(0, d.n_vocab, n_tok + 1).astype(np.int32)
+        for tk, p0 in ((toks[:n_tok], 0), (toks[n_tok:], n_tok)):
+            hid, lg, am = w.decode(tokens=torch.from_numpy(tk).cuda(), pos0=p0, want_argmax=True)
+            h_ref, l_ref = oracle.model_eval(ho, d, tokens=tk, pos0=p0)
+            nh, nl = _nmse(hid.cpu().numpy(), h_ref), _nmse(lg.cpu().numpy(), l_ref)
+            print(f"{name} n_ctx {n_ctx} tokens {len(tk)}: hidden NMSE {nh:.3e} logits NMSE {nl:.3e}")
+            assert nh < bound and nl < bound, (n_ctx, len(tk), nh, nl)
+            assert int(am.item()) == int(np.argmax(lg.cpu().numpy()))
+        ran = _attn_forms(w)
+        print(f"{name} n_ctx {n_ctx}: layer passes per attention form {ran}")
+        assert ran is None or ran == [d.n_layer if i == form else 0 for i in range(5)], (n_ctx, ran)
+        oracle.model_free(ho)
+        w.close()

@@ -1421,6 +1421,70 @@ def test_cached_attention_score_buffer_sized_for_max_keys_and_each_flag_on_its_o
     assert err <= 3e-3 * max(1.0, np.abs(want).max())
 
 
+@pytest.mark.parametrize("form", ["cached", "rope_fused", "decode"])
+def test_per_head_attention_beyond_48_kib_of_lds_twice_in_one_process(P, form):
+    """The three per-head launchers whose opt-in to more than 48 KiB of dynamic LDS goes through pm_allow_big_lds (pm355_kernels.h): pm355_attn_cached with
+    max_keys = 0, pm355_attn_rope_fused and pm355_attn_decode on a cache of 16384 cells - the score buffer is sized for n_ctx, about 66 KiB - with 300 cells
+    attended (beyond the 256-cell keys-in-lanes path: the buffer is used). Each is called twice: the first launch sets the attribute, the second makes no
+    runtime call, and both give the same bits. Against float64 softmax attention under the bound of
+    test_cached_attention_score_buffer_sized_for_max_keys_and_each_flag_on_its_own; attn_cached also against max_keys = 512 (the same kernel, a
+    48 KiB-free buffer): bit-equal."""
+    torch = P.torch
+    rng = np.random.default_rng(211)
+    H, Hkv, dh, n_ctx, n_kv = 2, 1, 64, 16384, 300
+    Nkv, pos = Hkv * dh, n_kv - 1
+    scale = 1.0 / np.sqrt(dh)
+    q = rng.normal(0, 1, (H, dh)).astype(np.float32)
+    K = rng.normal(0, 1, (n_kv, Nkv)).astype(np.float16)
+    V = rng.normal(0, 1, (n_kv, Nkv)).astype(np.float16)
+    k_new = rng.normal(0, 1, Nkv).astype(np.float32)
+    v_new = rng.normal(0, 1, Nkv).astype(np.float32)
+
+    def rope(x):                                 # NORM mode at position `pos`, float64 (ggml_compute_forward_rope_f32: pairs (2 i, 2 i + 1))
+        x = x.astype(np.float64).reshape(-1, dh // 2, 2)
+        th = pos * 10000.0 ** (-2.0 * np.arange(dh // 2) / dh)
+        c, s_ = np.cos(th)[None, :], np.sin(th)[None, :]
+        return np.stack([x[..., 0] * c - x[..., 1] * s_, x[..., 0] * s_ + x[..., 1] * c], axis=-1).reshape(-1, dh)
+
+    if form == "rope_fused":                     # the launch rotates q and k and stores the token's K row / V column in cell `pos` itself
+        qr = rope(q).astype(np.float16).astype(np.float32)
+        K[pos] = rope(k_new).reshape(-1).astype(np.float16)
+        V[pos] = v_new.astype(np.float16)
+        filled = pos
+    else:
+        q = qr = q.astype(np.float16).astype(np.float32)       # attn_cached reads rounded rows, attn_decode rounds them itself: the same values
+        filled = n_kv
+    kc = torch.zeros((n_ctx, Nkv), dtype=torch.float16, device="cuda")
+    kc[:filled] = torch.from_numpy(K[:filled]).cuda()
+    vc = torch.zeros((Nkv, n_ctx), dtype=torch.float16, device="cuda")
+    vc[:, :filled] = torch.from_numpy(np.ascontiguousarray(V[:filled].T)).cuda()
+    kci, vci = kc.view(torch.int16), vc.view(torch.int16)
+    qd = torch.from_numpy(q.reshape(1, -1)).cuda()
+    pd = torch.tensor([pos], dtype=torch.int32, device="cuda")
+
+    def run():
+        if form == "cached":
+            return P.attn_cached(qd, kci, vci, pd, H, Hkv, dh, n_ctx, scale, max_keys=0)
+        if form == "decode":
+            return P.attn_decode(qd, kci, vci, pos, H, Hkv, dh, n_ctx, scale)
+        return P.attn_rope_fused(qd.reshape(-1), torch.from_numpy(k_new).cuda(), torch.from_numpy(v_new).cuda(), kci, vci, pos, H, Hkv, dh, n_ctx, scale)
+    first = run().cpu().numpy().copy()
+    second = run().cpu().numpy().copy()
+    assert np.array_equal(first.view(np.uint32), second.view(np.uint32))
+    if form == "cached":
+        small = P.attn_cached(qd, kci, vci, pd, H, Hkv, dh, n_ctx, scale, max_keys=512).cpu().numpy()
+        assert np.array_equal(first.view(np.uint32), small.view(np.uint32))
+    want = np.zeros((H, dh))
+    for h in range(H):
+        hk = h // (H // Hkv)
+        s = K[:, hk * dh:(hk + 1) * dh].astype(np.float64) @ qr[h].astype(np.float64) * scale
+        p = np.exp(s - s.max()); p /= p.sum()
+        want[h] = p @ V[:, hk * dh:(hk + 1) * dh].astype(np.float64)
+    err = np.abs(first.reshape(H, dh).astype(np.float64) - want).max()
+    print(f"{form}: max |d out| {err:.3g}, max |out| {np.abs(want).max():.3g}")
+    assert err <= 3e-3 * max(1.0, np.abs(want).max())
+
+
 @pytest.mark.parametrize("flags", [0, 1, 2])
 @pytest.mark.parametrize("form", ["rope_fused", "long"])
 def test_attn_token_f16_caches_cell_mask_and_each_layout_flag_alone(P, form, flags):
