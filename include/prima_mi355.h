@@ -271,7 +271,7 @@ PM355_API int pm355_attn_rope_fused(const float * q, const float * k, const floa
                                     const int32_t * d_pos0, const float * freq_factors, float * out,
                                     int n_head, int n_head_kv, int head_dim, int n_ctx, float kq_scale,
                                     const pm355_rope_params * rp, pm355_stream_t stream);
-/* ggml-graph form of pm355_attn_rope_fused / the split path, what the plug-in's graph_compute lowers the node chain
+/* ggml-graph form of pm355_attn_rope_fused / the split path, what the plug-in's graph_compute lowers (through pm355_attn_token_plan / _run below) the node chain
  *   ROPE(Qcur) ROPE(Kcur) CPY(K -> k_cache_view) CPY(V^T -> v_cache_view) MUL_MAT(k, q) SOFT_MAX(kq, KQ_mask, scale) MUL_MAT(v, kq) CONT
  * of llm_build_kv (src/llama.cpp:10167-10205) to for ONE token: the RoPE position comes from the graph's inp_pos tensor
  * (d_pos[0]); the cache cell the token is stored in and the number of cells attended (kv_self.head / kv_self.n,
@@ -305,6 +305,35 @@ typedef struct {
 #define PM355_ATTN_K_Q8_0     4
 #define PM355_ATTN_V_Q8_0     8
 PM355_API int pm355_attn_token(const pm355_attn_token_args * a, const pm355_rope_params * rp, pm355_stream_t stream);
+/* The forms one token's attention takes in ggml-graph mode, and the one place that says which of them serves a layer. pm355_attn_token_plan is host
+ * arithmetic: no device needed, no pointer taken. It answers with a form, the cells (`max_keys`) that form's LDS score buffer or grid is sized for, the
+ * floats of scratch the form needs (0: none; zeroed once after allocation) and whether the form reads ROTATED query rows from caches that already hold
+ * the token (CACHED, CACHED_LONG: the wq | wk | wv launch ran with its RoPE + KV-store epilogue, pm355_mul_mat_vec_qkv) or the raw projections.
+ * A form it names is one its launcher serves: pm355_attn_token_run cannot refuse it for the shape or mode given here. FORM_NONE: no form serves the layer.
+ *   n_kv        cells attended now, 1 .. n_ctx: from split_min cells on a layer takes a long-context form (keys split over workgroups) where one serves
+ *               its shape, sized for a power-of-two bucket (>= 1024, <= n_ctx) of n_kv; below, a per-head form sized for split_min + 32 cells - or
+ *               for n_ctx where no long-context form serves the shape
+ *   flags       PM355_ATTN_* of the caches and the mask
+ *   attn_mfma   the matrix-core long-context kernel (CACHED_LONG, Q8_LONG) is allowed
+ *   rotated_q   the caller CAN deliver rotated rows (pm355_mul_mat_vec_qkv_check_ex accepted its launch); rope_mode / rope_n_dims as pm355_rope_params
+ *   scratch     the caller can provide scratch memory
+ *   n_cus       CUs of the device the plan is for, <= 0: the current device's */
+enum { PM355_ATTN_FORM_NONE = 0,
+       PM355_ATTN_FORM_ROPE_FUSED = 1,   /* raw projections, one workgroup per head (layer_ops.hip) */
+       PM355_ATTN_FORM_FLASH = 2,        /* raw projections, long context in one launch (attn_flash.hip) */
+       PM355_ATTN_FORM_SPLIT3 = 3,       /* the same in three launches (attn_split.hip): what PM355_ATTN_FLASH=0 turns FLASH into */
+       PM355_ATTN_FORM_Q8_TOKEN = 4,     /* Q8_0 caches, raw projections, one workgroup per head (attn_q8.hip) */
+       PM355_ATTN_FORM_Q8_LONG = 5,      /* Q8_0 caches, long context: RoPE + quantizing store, then attn_flash_mfma.hip over the cached cells */
+       PM355_ATTN_FORM_CACHED = 6,       /* rotated rows, one workgroup per head (attn_cached.hip) */
+       PM355_ATTN_FORM_CACHED_LONG = 7 };/* rotated rows, long context on the matrix cores (attn_flash_mfma.hip) */
+typedef struct { int32_t n_head, n_head_kv, head_dim, n_ctx, n_kv, flags, split_min, attn_mfma, rotated_q, rope_mode, rope_n_dims, scratch, n_cus; } pm355_attn_plan_in;
+typedef struct { int32_t form, cells, rotated_q, pad_; int64_t scratch_floats; } pm355_attn_plan_out;
+PM355_API int pm355_attn_token_plan(const pm355_attn_plan_in * in, pm355_attn_plan_out * out);
+/* Runs `form` on the argument block (max_keys = the plan's cells, scratch = the plan's floats; `split` is not read). The raw-projection forms take q / k / v
+ * and rp as pm355_attn_token does; for CACHED / CACHED_LONG q holds the rotated rows, k / v / freq_factors are not read, rp may be NULL and the cells come
+ * from d_cell_nkv (or, when that is NULL, from d_pos[0] as in pm355_attn_cached). pm355_attn_token, pm355_attn_cached and pm355_attn_cached_long
+ * fix the form from their arguments and run it here. */
+PM355_API int pm355_attn_token_run(int form, const pm355_attn_token_args * a, const pm355_rope_params * rp, pm355_stream_t stream);
 /* Single-token decode with the RoPE and the KV store in the EPILOGUE of the wq | wk | wv launch (NORM-mode rope - build_llama - and, with
  * rope_neox set, NEOX pairs (i, i + n_rot / 2) - build_qwen2, ggml.c:14238-14253 - where n_rot == head_dim and the row slices are powers of two):
  *   pm355_rope_table       this token's cos / sin per rotation pair, table[2 i] / table[2 i + 1], built with the reference's running
@@ -315,7 +344,8 @@ PM355_API int pm355_attn_token(const pm355_attn_token_args * a, const pm355_rope
  *                          K.q, ggml.c:12445-12473) -> jobs[0].y as f32, k -> F16 row of cache cell d_cell_nkv[0] (or d_pos[0] when
  *                          d_cell_nkv == NULL), v -> F16 V cache (llm_build_kv_store, src/llama.cpp:9688-9716). jobs[1].y / jobs[2].y unused.
  *   pm355_attn_cached      MUL_MAT(k, q) -> SOFT_MAX_EXT -> MUL_MAT(v, kq) over cells [0, d_cell_nkv[1]) (or [0, d_pos[0]]) that are all in
- *                          the cache; same rounding points and mask / flags as pm355_attn_token's one-workgroup-per-head path. */
+ *                          the cache; same rounding points and mask / flags as pm355_attn_token's one-workgroup-per-head path
+ *                          (PM355_ATTN_FORM_CACHED of pm355_attn_token_run, which is what the plug-in calls). */
 typedef struct {
     const float * rope_table; const int32_t * d_pos; const int32_t * d_cell_nkv; void * k_cache; void * v_cache;
     int32_t n_head_kv, head_dim, n_ctx, n_rot /* rope n_dims */, v_rowmajor, rope_neox /* rope mode & 2 */;
@@ -418,6 +448,8 @@ PM355_API int pm355_op_soft_max(const pm355_tensor * a, const pm355_tensor * mas
  * [n_kv, >= N] or NULL, dst F32 [D, H, N]; scale, ALiBi max_bias, logit softcap as in ggml_flash_attn_ext (ggml.h:1757) */
 PM355_API int pm355_op_flash_attn_ext(const pm355_tensor * q, const pm355_tensor * k, const pm355_tensor * v, const pm355_tensor * mask,
                                       const pm355_tensor * dst, float scale, float max_bias, float logit_softcap, pm355_stream_t stream);
+/* 1 when one query's scores over n_kv cells fit the LDS of pm355_op_flash_attn_ext's kernels (F16 or Q8_0 K / V), else 0. No device work. */
+PM355_API int pm355_op_flash_attn_ext_fits(int64_t head_dim, int64_t n_kv);
 PM355_API int pm355_op_rope(const pm355_tensor * a, const int32_t * d_pos, const float * freq_factors, const pm355_tensor * dst,
                             const pm355_rope_params * rp, pm355_stream_t stream);
 /* MUL_MAT with F16 / F32 src0 (the K.q and V.p products of llm_build_kqv): src1 F32 rounded to F16 when src0 is F16; or with a Q8_0 src0 in

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libprima_mi355.so")
 PROBE_LIB = os.path.join(HERE, "libprima_mi355_probe.so")
 SOURCES = ["c_api.hip", "quantize.hip", "mmvq.hip", "mmvq_cols.hip", "repack.hip", "layer_ops.hip", "ggml_ops.hip", "engine.hip", "mmq.hip", "mmq_pf.hip", "mmq_i8.hip", "mmq_big.hip",
-           "attn_prefill.hip", "attn_cached.hip", "attn_flash_mfma.hip", "attn_split.hip", "attn_flash.hip", "attn_q8.hip", "ring.hip", "upload.hip", "ts.hip"]
+           "attn_prefill.hip", "attn_cached.hip", "attn_flash_mfma.hip", "attn_split.hip", "attn_flash.hip", "attn_q8.hip", "attn_plan.hip", "ring.hip", "upload.hip", "ts.hip"]
 # round 5's measured-slower forms of the decode layer (sum-of-squares partials, attention tail, persistent engine): a library of their own, loaded by their tests
 EXP_LIB = os.path.join(HERE, "libprima_mi355_exp.so")
 EXP_SOURCES = SOURCES + ["decode_engine.hip"]

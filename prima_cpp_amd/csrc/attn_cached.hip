@@ -153,13 +153,14 @@ void pm_launch_rope_table(const pm_rope_cfg & c, const int32_t * pos, const int3
 }
 
 // q = rotated, F16-rounded query rows; caches already hold this token
+bool pm_attn_cached_ok(const pm_attn_tok & t) {
+    return pm_attn_head_shape_ok(t) && t.n_tok >= 1 && !(t.n_tok > 1 && t.dyn) && !t.rope && !t.k_q8 && !t.v_q8 && (t.pos || t.dyn);
+}
 int pm_launch_attn_cached(const pm_attn_tok & t, hipStream_t st) {
+    if (!pm_attn_cached_ok(t)) return -1;
     const int dh = t.dh;
-    if ((dh != 64 && dh != 128 && dh != 256) || t.n_ctx % 8 || t.n_tok < 1 || (t.n_tok > 1 && t.dyn)) return -1;
     const size_t lds = pm_attn_head_lds(dh, t.n_ctx, t.v_rowmajor, t.cells);
-    if (lds > PM_ATTN_LDS_MAX || t.rope || t.k_q8 || t.v_q8) return -1;
     const int32_t * pos0 = t.pos ? t.pos : t.dyn;   // ggml-graph mode: cells come from dyn; keep every pointer the kernel may touch valid
-    if (!pos0) return -1;
     auto launch = [&](auto kern) {
         pm_allow_big_lds((const void *) kern, lds);
         AttnP a = {t.q, nullptr, nullptr, (uint16_t *) t.kc, (uint16_t *) t.vc, pos0, t.seq, t.seq_stride, nullptr, t.out, t.H, t.Hkv, t.n_ctx, t.scale,

@@ -25,7 +25,7 @@
 namespace {
 
 constexpr int CK = PM_FLASH_CK;                  // keys per chunk (one pass of the workgroup)
-constexpr int RMAX = 8;
+constexpr int RMAX = PM_ATTN_GROUP_MAX;
 
 struct FlashP {
     const float * q, * k, * v; uint16_t * kc, * vc; const int32_t * pos0_ptr, * seq_ptr; long seq_stride;
@@ -331,10 +331,12 @@ __global__ __launch_bounds__(256) void attn_flash_kernel(FlashP p) {
 // scratch: pm_attn_flash_layout (the caller zeroes it once after allocating it)
 // q, k, v = the RAW projections of the token; RoPE, KV store and attention over cells [0, n_kv) happen in this one launch.
 // max_cells bounds the cells attended (sizes the grid: spans beyond n_kv exit at once); 0 = n_ctx. -1: unsupported shape.
+bool pm_attn_flash_ok(const pm_attn_tok & a) {
+    return pm_attn_split_heads_ok(a.H, a.Hkv, a.dh) && a.n_ctx % 8 == 0 && a.scratch && a.rope && !a.k_q8 && !a.v_q8 && a.n_tok == 1;
+}
 int pm_launch_attn_flash(const pm_attn_tok & a, hipStream_t st) {
+    if (!pm_attn_flash_ok(a)) return -1;
     const int H = a.H, Hkv = a.Hkv, dh = a.dh, n_ctx = a.n_ctx; float * const scratch = a.scratch;
-    if ((dh != 64 && dh != 128) || H % Hkv || H / Hkv > RMAX || n_ctx % 8 || !scratch) return -1;
-    if (!a.rope || a.k_q8 || a.v_q8 || a.n_tok != 1) return -1;
     const pm_flash_scratch lay = pm_attn_flash_layout(H, Hkv, dh, n_ctx);
     const int cells = a.cells > 0 && a.cells < n_ctx ? a.cells : n_ctx;
     // span = keys per workgroup: 128 up to 8k cells, then grown so that a KV head never has more than 64 partials to merge

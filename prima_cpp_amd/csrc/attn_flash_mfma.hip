@@ -391,20 +391,23 @@ __global__ __launch_bounds__(256, 2) void attn_flash_mfma_kernel(FlashM p) {
 // Shapes the matrix-core kernel serves: head_dim 64 / 128, <= 16 query heads per KV head, n_ctx % 8 == 0, and <= 16 KV heads - the arrival
 // counters live at ticket[g] / ticket[16 + g] and the bounded spin of the merging workgroups assumes that the whole grid (n_head_kv x <= 64 spans
 // <= 2 x CUs workgroups of 4 waves) is resident. MHA models (Llama-2-7B / 13B: 32 / 40 KV heads) keep the round-2 kernel (attn_flash.hip).
-int pm_attn_flash_cached_ok(int H, int Hkv, int dh, int n_ctx) {
-    if ((dh != 64 && dh != 128) || Hkv < 1 || H % Hkv || H / Hkv > RMAXM || n_ctx % 8 || Hkv > 16) return -1;
+bool pm_attn_flash_cached_shape_ok(int H, int Hkv, int dh, int n_ctx, int n_cus) {
+    if ((dh != 64 && dh != 128) || Hkv < 1 || H % Hkv || H / Hkv > RMAXM || n_ctx % 8 || Hkv > 16) return false;
     int parts = 256 / Hkv;
     parts = parts < 16 ? 16 : parts > 64 ? 64 : parts;
-    return Hkv * parts <= 2 * pm_device_cus() ? 0 : -1;
+    return Hkv * parts <= 2 * (n_cus > 0 ? n_cus : pm_device_cus());
+}
+bool pm_attn_flash_cached_ok(const pm_attn_tok & a, int n_cus) {
+    if (!a.scratch || !pm_attn_flash_cached_shape_ok(a.H, a.Hkv, a.dh, a.n_ctx, n_cus) || a.rope || a.n_tok != 1) return false;
+    if ((a.k_q8 || a.v_q8) && (!a.v_rowmajor || a.seq)) return false;     // Q8_0 caches: flash-attention layout (row-major V), one sequence slab
+    return a.pos || a.dyn;
 }
 
 int pm_launch_attn_flash_cached(const pm_attn_tok & a, hipStream_t st) {
+    if (!pm_attn_flash_cached_ok(a)) return -1;
     const int H = a.H, Hkv = a.Hkv, dh = a.dh, n_ctx = a.n_ctx;
     const bool k_q8 = a.k_q8, v_q8 = a.v_q8, v_rowmajor = a.v_rowmajor; float * const scratch = a.scratch;
-    if (!scratch || pm_attn_flash_cached_ok(H, Hkv, dh, n_ctx) || a.rope || a.n_tok != 1) return -1;
-    if ((k_q8 || v_q8) && (!v_rowmajor || a.seq)) return -1;        // Q8_0 caches: flash-attention layout (row-major V), one sequence slab
     const int32_t * pos0 = a.pos ? a.pos : a.dyn;
-    if (!pos0) return -1;
     const pm_flash_scratch lay = pm_attn_flash_layout(H, Hkv, dh, n_ctx);
     const int cells = a.cells > 0 && a.cells < n_ctx ? a.cells : n_ctx;
     // spans: 128 keys each until the KV heads together fill the CUs (256 workgroups: 32 spans per head at 8 KV heads - measured against 64

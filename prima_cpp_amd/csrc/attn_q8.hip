@@ -402,9 +402,8 @@ int pm_launch_flash_attn_ext_q8(const pm355_tensor * q, const pm355_tensor * k, 
     const int D = (int) q->ne[0];
     if ((D != 64 && D != 128 && D != 256) || (!kq8 && !vq8)) return -1;
     if ((kq8 ? k->nb[0] != QB : k->nb[0] != 2) || (vq8 ? v->nb[0] != QB : v->nb[0] != 2)) return -1;
-    const int nslot = 256 / (D / 8);
-    const size_t lds = ((size_t) D + (((size_t) k->ne[1] + 3) & ~(size_t) 3) + (size_t) nslot * D) * 4;
-    if (lds > 150 * 1024) return -2;
+    const size_t lds = pm_flash_attn_ext_lds(D, k->ne[1]);
+    if (lds > PM_ATTN_LDS_MAX) return -2;
     if (softcap != 0.0f) scale /= softcap;
     const dim3 grid((unsigned) q->ne[1], (unsigned) q->ne[2], (unsigned) q->ne[3]);
     auto go = [&](auto kern) {
@@ -420,9 +419,14 @@ int pm_launch_flash_attn_ext_q8(const pm355_tensor * q, const pm355_tensor * k, 
 
 // one token, long context: RoPE + (quantizing) KV store in one small launch (t.out receives the operand rows of the K.q product), then the caller
 // runs pm_launch_attn_flash_cached over the cached cells. Row-major caches. -1: unsupported
+// what both token kernels of this file ask of the shape and the mode
+static bool q8_token_mode_ok(const pm_attn_tok & t) {
+    return (t.dh == 64 || t.dh == 128) && t.Hkv >= 1 && t.H % t.Hkv == 0 && (t.k_q8 || t.v_q8) && t.dyn && t.rope && t.v_rowmajor && !t.seq && t.n_tok == 1;
+}
+bool pm_attn_q8_token_prep_ok(const pm_attn_tok & t) { return q8_token_mode_ok(t) && t.out; }
 int pm_launch_q8_token_prep(const pm_attn_tok & t, hipStream_t st) {
+    if (!pm_attn_q8_token_prep_ok(t)) return -1;
     const int H = t.H, dh = t.dh; const bool k_q8 = t.k_q8, v_q8 = t.v_q8;
-    if ((dh != 64 && dh != 128) || H % t.Hkv || (!k_q8 && !v_q8) || !t.dyn || !t.out || !t.rope || !t.v_rowmajor || t.seq || t.n_tok != 1) return -1;
     Q8TokP a = {};
     a.q = t.q; a.k = t.k; a.v = t.v; a.kc = (uint8_t *) t.kc; a.vc = (uint8_t *) t.vc; a.pos = t.pos; a.dyn = t.dyn; a.ff = t.freq_factors;
     a.H = H; a.Hkv = t.Hkv; a.n_ctx = t.n_ctx; a.r = rope_p(*t.rope);
@@ -436,13 +440,16 @@ int pm_launch_q8_token_prep(const pm_attn_tok & t, hipStream_t st) {
 }
 
 // one token, one launch: RoPE + KV store (quantizing) + attention over cells [0, dyn[1]); row-major caches. -1: unsupported
-int pm_launch_attn_q8_token(const pm_attn_tok & t, hipStream_t st) {
-    const int H = t.H, dh = t.dh; const bool k_q8 = t.k_q8, v_q8 = t.v_q8;
-    if ((dh != 64 && dh != 128) || H % t.Hkv || (!k_q8 && !v_q8) || !t.dyn || !t.rope || !t.v_rowmajor || t.seq || t.n_tok != 1) return -1;
-    // (this kernel's own LDS layout - three head rows, always the row-major V slots - not pm_attn_head_lds)
+// (this kernel's own LDS layout - three head rows, always the row-major V slots - not pm_attn_head_lds)
+static size_t q8_token_lds(const pm_attn_tok & t) {
     const int keys = t.cells > 0 ? t.cells : t.n_ctx;
-    const size_t lds = ((size_t) 3 * dh + 2048 + (size_t) ((keys + 7) & ~7) + 8) * 4;
-    if (lds > PM_ATTN_LDS_MAX) return -1;
+    return ((size_t) 3 * t.dh + 2048 + (size_t) ((keys + 7) & ~7) + 8) * 4;
+}
+bool pm_attn_q8_token_ok(const pm_attn_tok & t) { return q8_token_mode_ok(t) && q8_token_lds(t) <= PM_ATTN_LDS_MAX; }
+int pm_launch_attn_q8_token(const pm_attn_tok & t, hipStream_t st) {
+    if (!pm_attn_q8_token_ok(t)) return -1;
+    const int H = t.H, dh = t.dh; const bool k_q8 = t.k_q8, v_q8 = t.v_q8;
+    const size_t lds = q8_token_lds(t);
     Q8TokP a;
     a.q = t.q; a.k = t.k; a.v = t.v; a.kc = (uint8_t *) t.kc; a.vc = (uint8_t *) t.vc; a.pos = t.pos; a.dyn = t.dyn; a.mask = t.mask; a.mask_f16 = t.mask_f16;
     a.ff = t.freq_factors; a.out = t.out; a.H = H; a.Hkv = t.Hkv; a.n_ctx = t.n_ctx; a.scale = t.scale; a.r = rope_p(*t.rope);

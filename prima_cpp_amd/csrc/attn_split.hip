@@ -21,7 +21,7 @@
 namespace {
 
 constexpr int CK = 128;                          // keys per workgroup (256: half the workgroups, 1.4x the latency chain per workgroup)
-constexpr int RMAX = 8;                          // query heads per KV head (GQA group) handled by one workgroup
+constexpr int RMAX = PM_ATTN_GROUP_MAX;                          // query heads per KV head (GQA group) handled by one workgroup
 
 struct SplitP {
     const float * q; const uint16_t * kc; const uint16_t * vc; const int32_t * pos0_ptr; const int32_t * seq_ptr; long seq_stride;
@@ -300,9 +300,12 @@ size_t pm_attn_split_scratch_floats(int H, int dh, int n_ctx) {
 
 // rope == nullptr: q = this token's ROTATED queries [H*dh] f32 and the caches already hold its K row / V column (k, v unused).
 // rope != nullptr: q, k, v = the RAW projections; the rotation, the KV store and the attention are done here (3 launches).
+bool pm_attn_split_ok(const pm_attn_tok & a) {
+    return pm_attn_split_heads_ok(a.H, a.Hkv, a.dh) && a.n_ctx % 8 == 0 && a.scratch && !a.k_q8 && !a.v_q8 && !a.cells && a.n_tok == 1;
+}
 int pm_launch_attn_split(const pm_attn_tok & a, hipStream_t st) {
+    if (!pm_attn_split_ok(a)) return -1;
     const int H = a.H, Hkv = a.Hkv, dh = a.dh, n_ctx = a.n_ctx;
-    if ((dh != 64 && dh != 128) || H % Hkv || H / Hkv > RMAX || n_ctx % 8 || !a.scratch || a.k_q8 || a.v_q8 || a.cells || a.n_tok != 1) return -1;
     const int nchunk = (n_ctx + CK - 1) / CK;
     SplitP p = {};
     p.q = a.q; p.kc = (const uint16_t *) a.kc; p.vc = (const uint16_t *) a.vc; p.pos0_ptr = a.pos; p.seq_ptr = a.seq; p.seq_stride = a.seq_stride;

@@ -449,7 +449,7 @@ int pm355_attn_rope_fused(const float * q, const float * k, const float * v, voi
     return 0;
 }
 int pm355_rope_table(const pm355_rope_params * rp, const int32_t * d_pos, const float * ff, float * table, pm355_stream_t st) {
-    if (!rp || rp->n_dims % 2 || rp->n_dims > 256 || !d_pos || !table) return fail(PM355_E_SHAPE, "rope_table: n_dims (even, <= 256), d_pos and table required");
+    if (!rp || rp->n_dims % 2 || rp->n_dims > PM_ROPE_TABLE_DIMS_MAX || !d_pos || !table) return fail(PM355_E_SHAPE, "rope_table: n_dims (even, <= 256), d_pos and table required");
     pm_launch_rope_table(pm_rope_cfg_of(*rp), d_pos, nullptr, ff, table, S(st));
     HIP_TRY(hipGetLastError());
     return 0;
@@ -551,77 +551,45 @@ int pm355_mul_mat_vec_fused_plan(const pm355_matvec_job * jobs, int njobs, int64
 int pm355_mul_mat_vec_qkv_check(const pm355_matvec_job * jobs, int64_t K, int n_head_kv, int head_dim, int n_rot) {
     return pm355_mul_mat_vec_qkv_check_ex(jobs, K, n_head_kv, head_dim, n_rot, 0);
 }
-int pm355_attn_cached(const float * q_rot, void * kc, void * vc, const int32_t * d_pos, const int32_t * d_cell_nkv, const void * mask,
-                      float * out, int H, int Hkv, int dh, int n_ctx, float kq_scale, int max_keys, int flags, pm355_stream_t st) {
-    if (!q_rot || !kc || !vc || !out || (!d_pos && !d_cell_nkv)) return fail(PM355_E_SHAPE, "attn_cached: null pointer");
-    pm_attn_tok t = {};
-    t.q = q_rot; t.kc = kc; t.vc = vc; t.pos = d_pos; t.dyn = d_cell_nkv; t.mask = mask; t.out = out;
-    t.H = H; t.Hkv = Hkv; t.dh = dh; t.n_ctx = n_ctx; t.scale = kq_scale; t.cells = max_keys;
-    t.v_rowmajor = flags & PM355_ATTN_V_ROWMAJOR; t.mask_f16 = flags & PM355_ATTN_MASK_F16;
-    if (pm_launch_attn_cached(t, S(st)))
-        return fail(PM355_E_UNSUPPORTED, "attn_cached: head_dim must be 64/128/256, n_ctx % 8 == 0 and max_keys fit LDS");
+// the single-token attention entries: each fixes the form and its argument block, pm_attn_token_run (attn_plan.hip) holds the one switch
+int pm355_attn_token_run(int form, const pm355_attn_token_args * a, const pm355_rope_params * rp, pm355_stream_t st) {
+    if (!a) return fail(PM355_E_SHAPE, "attn_token_run: arguments");
+    const char * why = nullptr;
+    if (const int rc = pm_attn_token_run(form, *a, rp, S(st), &why)) return fail(rc, why);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+int pm355_op_flash_attn_ext_fits(int64_t head_dim, int64_t n_kv) { return head_dim >= 8 && n_kv >= 0 && pm_flash_attn_ext_lds(head_dim, n_kv) <= PM_ATTN_LDS_MAX; }
+int pm355_attn_token_plan(const pm355_attn_plan_in * in, pm355_attn_plan_out * out) {
+    if (!in || !out) return fail(PM355_E_SHAPE, "attn_token_plan: arguments");
+    pm_attn_token_plan(*in, *out);
+    return 0;
+}
+static pm355_attn_token_args cached_args(const float * q_rot, void * kc, void * vc, const int32_t * d_pos, const int32_t * d_cell_nkv, const void * mask, float * out,
+                                         float * scratch, int H, int Hkv, int dh, int n_ctx, float kq_scale, int max_keys, int flags) {
+    pm355_attn_token_args a = {};
+    a.q = q_rot; a.k_cache = kc; a.v_cache = vc; a.d_pos = d_pos; a.d_cell_nkv = d_cell_nkv; a.mask = mask; a.out = out; a.scratch = scratch;
+    a.n_head = H; a.n_head_kv = Hkv; a.head_dim = dh; a.n_ctx = n_ctx; a.max_keys = max_keys; a.kq_scale = kq_scale; a.flags = flags;
+    return a;
+}
+int pm355_attn_cached(const float * q_rot, void * kc, void * vc, const int32_t * d_pos, const int32_t * d_cell_nkv, const void * mask,
+                      float * out, int H, int Hkv, int dh, int n_ctx, float kq_scale, int max_keys, int flags, pm355_stream_t st) {
+    const pm355_attn_token_args a = cached_args(q_rot, kc, vc, d_pos, d_cell_nkv, mask, out, nullptr, H, Hkv, dh, n_ctx, kq_scale, max_keys,
+                                                flags & (PM355_ATTN_V_ROWMAJOR | PM355_ATTN_MASK_F16));      // (this entry never read another flag)
+    return pm355_attn_token_run(PM355_ATTN_FORM_CACHED, &a, nullptr, st);
 }
 int pm355_attn_cached_long(const float * q_rot, void * kc, void * vc, const int32_t * d_pos, const int32_t * d_cell_nkv, const void * mask,
                            float * out, float * scratch, int H, int Hkv, int dh, int n_ctx, float kq_scale, int max_cells, int flags, pm355_stream_t st) {
-    if (!q_rot || !kc || !vc || !out || !scratch || (!d_pos && !d_cell_nkv)) return fail(PM355_E_SHAPE, "attn_cached_long: null pointer");
-    if (flags & ~(PM355_ATTN_MASK_F16 | PM355_ATTN_V_ROWMAJOR | PM355_ATTN_K_Q8_0 | PM355_ATTN_V_Q8_0)) return fail(PM355_E_UNSUPPORTED, "attn_cached_long: unknown flag");
-    pm_attn_tok t = {};
-    t.q = q_rot; t.kc = kc; t.vc = vc; t.pos = d_pos; t.dyn = d_cell_nkv; t.mask = mask; t.out = out; t.scratch = scratch;
-    t.H = H; t.Hkv = Hkv; t.dh = dh; t.n_ctx = n_ctx; t.scale = kq_scale; t.cells = max_cells;
-    t.v_rowmajor = flags & PM355_ATTN_V_ROWMAJOR; t.mask_f16 = flags & PM355_ATTN_MASK_F16;
-    t.k_q8 = flags & PM355_ATTN_K_Q8_0; t.v_q8 = flags & PM355_ATTN_V_Q8_0;
-    if (pm_launch_attn_flash_cached(t, S(st)))
-        return fail(PM355_E_UNSUPPORTED, "attn_cached_long: head_dim must be 64/128, <= 16 query heads per KV head, n_ctx % 8 == 0; Q8_0 caches need row-major V");
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const pm355_attn_token_args a = cached_args(q_rot, kc, vc, d_pos, d_cell_nkv, mask, out, scratch, H, Hkv, dh, n_ctx, kq_scale, max_cells, flags);
+    return pm355_attn_token_run(PM355_ATTN_FORM_CACHED_LONG, &a, nullptr, st);
 }
-int pm355_attn_cached_long_check(int H, int Hkv, int dh, int n_ctx) { return pm_attn_flash_cached_ok(H, Hkv, dh, n_ctx) ? PM355_E_UNSUPPORTED : 0; }
+int pm355_attn_cached_long_check(int H, int Hkv, int dh, int n_ctx) { return pm_attn_flash_cached_shape_ok(H, Hkv, dh, n_ctx) ? 0 : PM355_E_UNSUPPORTED; }
 int pm355_attn_token(const pm355_attn_token_args * a, const pm355_rope_params * rp, pm355_stream_t st) {
-    if (!a || !rp || rp->n_dims % 2 || rp->n_dims > a->head_dim) return fail(PM355_E_SHAPE, "attn_token: n_dims");
-    if (!a->d_pos || !a->d_cell_nkv || !a->q || !a->k || !a->v || !a->k_cache || !a->v_cache || !a->out) return fail(PM355_E_SHAPE, "attn_token: null pointer");
-    const pm_rope_cfg c = pm_rope_cfg_of(*rp);
-    pm_attn_tok t = {};
-    t.q = a->q; t.k = a->k; t.v = a->v; t.kc = a->k_cache; t.vc = a->v_cache; t.pos = a->d_pos; t.dyn = a->d_cell_nkv; t.mask = a->mask;
-    t.freq_factors = a->freq_factors; t.out = a->out; t.scratch = a->scratch; t.rope = &c; t.cells = a->max_keys;
-    t.H = a->n_head; t.Hkv = a->n_head_kv; t.dh = a->head_dim; t.n_ctx = a->n_ctx; t.scale = a->kq_scale;
-    t.v_rowmajor = a->flags & PM355_ATTN_V_ROWMAJOR; t.mask_f16 = a->flags & PM355_ATTN_MASK_F16;
-    t.k_q8 = a->flags & PM355_ATTN_K_Q8_0; t.v_q8 = a->flags & PM355_ATTN_V_Q8_0;
+    if (!a) return fail(PM355_E_SHAPE, "attn_token: n_dims");
     (void) hipGetLastError();
-    if (t.k_q8 || t.v_q8) {
-        if (!(a->flags & PM355_ATTN_V_ROWMAJOR)) return fail(PM355_E_UNSUPPORTED, "attn_token: a quantized KV cache needs row-major V (flash-attention graphs)");
-        if (a->split) {
-            // long context: RoPE + quantizing KV store (one small launch), then scores and P.V on the matrix cores over the cached Q8_0 / F16 cells
-            // (attn_flash_mfma.hip); max_keys = cells the grid is sized for, scratch zeroed once after its allocation
-            if (!a->scratch) return fail(PM355_E_SHAPE, "attn_token(q8_0, long): scratch");
-            pm_attn_tok prep = t, cached = t;
-            prep.out = a->scratch + pm_attn_flash_layout(a->n_head, a->n_head_kv, a->head_dim, a->n_ctx).qrot;
-            cached.q = prep.out; cached.k = cached.v = nullptr; cached.pos = nullptr; cached.freq_factors = nullptr; cached.rope = nullptr;
-            if (pm_launch_q8_token_prep(prep, S(st)) || pm_launch_attn_flash_cached(cached, S(st)))
-                return fail(PM355_E_UNSUPPORTED, "attn_token(q8_0, long): head_dim 64/128, <= 16 query heads per KV head, <= 16 KV heads, n_ctx % 8 == 0");
-            HIP_TRY(hipGetLastError());
-            return 0;
-        }
-        if (pm_launch_attn_q8_token(t, S(st)))
-            return fail(PM355_E_UNSUPPORTED, "attn_token(q8_0): head_dim 64/128 and max_keys must fit LDS");
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    static const bool three_launch = [] { const char * e = getenv("PM355_ATTN_FLASH"); return e && e[0] == '0'; }();
-    if (a->split && !three_launch) {
-        // long context, ONE launch: flash-decoding with an in-launch merge (attn_flash.hip); max_keys (> 0) = cells the grid is sized for.
-        // The scratch must have been zeroed once after its allocation (ticket words).
-        if (pm_launch_attn_flash(t, S(st)))
-            return fail(PM355_E_UNSUPPORTED, "attn_token(flash): head_dim 64/128, at most 8 query heads per KV head, n_ctx % 8 == 0, scratch required");
-    } else if (a->split) {
-        t.cells = 0;                                  // (the three-launch form has nothing max_keys would size)
-        if (pm_launch_attn_split(t, S(st)))
-            return fail(PM355_E_UNSUPPORTED, "attn_token(split): head_dim 64/128, at most 8 query heads per KV head, n_ctx % 8 == 0, scratch required");
-    } else if (pm_launch_attn_rope_fused(t, S(st)))
-        return fail(PM355_E_UNSUPPORTED, "attn_token: head_dim must be 64/128/256, n_ctx % 8 == 0 and max_keys fit LDS");
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const bool q8 = a->flags & (PM355_ATTN_K_Q8_0 | PM355_ATTN_V_Q8_0);
+    const int form = q8 ? (a->split ? PM355_ATTN_FORM_Q8_LONG : PM355_ATTN_FORM_Q8_TOKEN) : a->split ? pm_attn_long_raw_form() : PM355_ATTN_FORM_ROPE_FUSED;
+    return pm355_attn_token_run(form, a, rp, st);
 }
 int pm355_set_i32x2(int32_t * d_p, int32_t a, int32_t b, pm355_stream_t st) { pm_launch_set_i32x2(d_p, a, b, S(st)); HIP_TRY(hipGetLastError()); return 0; }
 

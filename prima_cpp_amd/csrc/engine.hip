@@ -536,7 +536,7 @@ int run_layers_fused(pm355_model * m, const float * cur, float * d_x_out, const 
     // rope + KV store in the QKV epilogue: NORM-mode rope, one-workgroup-per-head attention regime
     // (NEOX rope - build_qwen2 - where every workgroup's slice of wq / wk holds both halves of its rotation pairs: pm_launch_gemv_fused tells)
     bool epi = m->qkv_epi && m->rope_tab && (m->rope.mode == 0 || m->rope.mode == 2) &&
-               (!m->long_ctx || (m->use_flash && m->attn_mfma && H / Hkv <= 8 && pm_attn_flash_cached_ok(H, Hkv, dh, hp.n_ctx) == 0));
+               (!m->long_ctx || (m->use_flash && m->attn_mfma && pm_attn_split_heads_ok(H, Hkv, dh) && pm_attn_flash_cached_shape_ok(H, Hkv, dh, hp.n_ctx)));
     if (epi) pm_launch_rope_table(m->rope, m->d_pos, m->d_ctl, (const float *) m->rope_freqs.d, m->rope_tab, st);
     bool tail = epi && !m->long_ctx && m->attn_tail && m->att_tk && Hkv <= 64;
     double * ss_wo = (m->use_ss && m->ss) ? m->ss : nullptr, * ss_dn = ss_wo ? m->ss + 256 : nullptr;
@@ -1016,7 +1016,7 @@ int pm355_model_finalize_seqs(pm355_model * m, int max_tokens, int n_seq) {
     if (ok && T > MMQ_MAX_TOKENS && !m->no_big) ok = A((void **) &m->tab_big, pm_mmq_big_table_bytes((int) ((maxK + 255) / 256 * 256), (int) T));
     if (!ok) return seterr(m, PM355_E_NOMEM, "finalize: scratch");
     const size_t long_scratch_bytes = pm_attn_long_scratch_floats(hp.n_head, hp.n_head_kv, hp.head_dim, hp.n_ctx) * 4;
-    if (hp.n_head / hp.n_head_kv <= 8 && (hp.head_dim == 64 || hp.head_dim == 128) &&
+    if (pm_attn_split_heads_ok(hp.n_head, hp.n_head_kv, hp.head_dim) &&
         !A((void **) &m->split_scratch, long_scratch_bytes)) return seterr(m, PM355_E_NOMEM, "finalize: attention scratch");
     if (m->split_scratch) (void) hipMemset(m->split_scratch, 0, long_scratch_bytes);       // (the flash kernels' tickets start at 0)
     if (m->n_slots) {

@@ -518,12 +518,11 @@ bool supports_op_impl(const struct ggml_tensor * op) {
                 if ((k->type != GGML_TYPE_Q8_0 && k->type != GGML_TYPE_F16) || (v->type != GGML_TYPE_Q8_0 && v->type != GGML_TYPE_F16)) return false;
                 if ((k->type == GGML_TYPE_Q8_0 && is_soa_tensor(k)) || (v->type == GGML_TYPE_Q8_0 && is_soa_tensor(v))) return false;
                 if ((D != 64 && D != 128 && D != 256) || a->nb[0] != 4 || max_bias != 0.0f || (m && m->type != GGML_TYPE_F16)) return false;
-                return (size_t) (D + ((k->ne[1] + 3) & ~3) + (256 / (D / 8)) * D) * 4 <= 150 * 1024;
+                return pm355_op_flash_attn_ext_fits(D, k->ne[1]) != 0;
             }
             if (a->type != GGML_TYPE_F32 || k->type != GGML_TYPE_F16 || v->type != GGML_TYPE_F16 || op->type != GGML_TYPE_F32) return false;
             if (D < 8 || D > 256 || a->nb[0] != 4 || k->nb[0] != 2 || v->nb[0] != 2 || (m && m->type != GGML_TYPE_F16)) return false;
-            const int64_t Dp = (D + 7) & ~7;
-            return (size_t) (Dp + ((k->ne[1] + 3) & ~3) + (256 / (Dp / 8)) * Dp) * 4 <= 150 * 1024;     // scores of one query live in LDS
+            return pm355_op_flash_attn_ext_fits(D, k->ne[1]) != 0;     // scores of one query live in LDS
         }
         case GGML_OP_GET_ROWS:
             return b->type == GGML_TYPE_I32 && ggml_is_contiguous(b) && b->ne[1] == 1 && b->ne[2] == 1 && b->ne[3] == 1 &&
@@ -690,22 +689,13 @@ bool run_plan(backend_ctx * c, struct ggml_cgraph * g, const mi355::plan & p) {
                 MI355_CHECK(pm355_mul_mat_vec_fused_ss(s.job, s.njobs, s.K, s.x, s.norm_w, s.eps, s.ss_out, s.ss_in, s.n_ss, c->stream));
                 break;
             case mi355::STEP_ATTN:
-                MI355_CHECK(pm355_attn_token(&s.attn, &s.rope, c->stream));
+                MI355_CHECK(pm355_attn_token_run(s.attn_form, &s.attn, &s.rope, c->stream));
                 break;
             case mi355::STEP_ROPE_TAB:
                 MI355_CHECK(pm355_rope_table(&s.rope, s.attn.d_pos, s.attn.freq_factors, (float *) s.qs.rope_table, c->stream));
                 break;
             case mi355::STEP_QKV:
                 MI355_CHECK(pm355_mul_mat_vec_qkv_ss(s.job, s.K, s.x, s.norm_w, s.eps, &s.qs, s.ss_in, s.n_ss, c->stream));
-                break;
-            case mi355::STEP_ATTN_CACHED:
-                if (s.attn.split) {
-                    MI355_CHECK(pm355_attn_cached_long(s.attn.q, s.attn.k_cache, s.attn.v_cache, nullptr, s.attn.d_cell_nkv, s.attn.mask, s.attn.out, s.attn.scratch,
-                                                       s.attn.n_head, s.attn.n_head_kv, s.attn.head_dim, s.attn.n_ctx, s.attn.kq_scale, s.attn.max_keys, s.attn.flags, c->stream));
-                    break;
-                }
-                MI355_CHECK(pm355_attn_cached(s.attn.q, s.attn.k_cache, s.attn.v_cache, nullptr, s.attn.d_cell_nkv, s.attn.mask, s.attn.out, s.attn.n_head,
-                                              s.attn.n_head_kv, s.attn.head_dim, s.attn.n_ctx, s.attn.kq_scale, s.attn.max_keys, s.attn.flags, c->stream));
                 break;
             case mi355::STEP_ATTN_BATCH:
                 MI355_CHECK(pm355_attn_prefill_masked_ex(s.ab.q, s.ab.kc, s.ab.vc, s.ab.mask, s.ab.mask_stride, s.ab.out, s.ab.n_tokens, s.ab.n_head,
@@ -741,9 +731,12 @@ void print_plan(const backend_ctx * c, struct ggml_cgraph * g, const mi355::plan
         } else if (s.kind == mi355::STEP_ATTN_BATCH) {
             fprintf(stderr, "  [%d,%d) batch attention T=%d H=%d Hkv=%d dh=%d n_kv=%d (MFMA, masked)\n", s.node_lo, s.node_hi, s.ab.n_tokens, s.ab.n_head,
                     s.ab.n_head_kv, s.ab.head_dim, s.ab.n_kv);
-        } else if (s.kind == mi355::STEP_ATTN || s.kind == mi355::STEP_ATTN_CACHED) {
+        } else if (s.kind == mi355::STEP_ATTN) {
+            const int f = s.attn_form;                                // four words: per head or keys split over workgroups, raw projections or cached cells
+            const bool per_head = f == PM355_ATTN_FORM_ROPE_FUSED || f == PM355_ATTN_FORM_Q8_TOKEN || f == PM355_ATTN_FORM_CACHED;
+            const bool cached = f == PM355_ATTN_FORM_CACHED || f == PM355_ATTN_FORM_CACHED_LONG;
             fprintf(stderr, "  [%d,%d) attention H=%d Hkv=%d dh=%d n_ctx=%d %s mask=%d ff=%d\n", s.node_lo, s.node_hi, s.attn.n_head, s.attn.n_head_kv, s.attn.head_dim,
-                    s.attn.n_ctx, s.kind == mi355::STEP_ATTN_CACHED ? (s.attn.split ? "cached-split" : "cached") : (s.attn.split ? "split" : "fused"), s.attn.mask != nullptr, s.attn.freq_factors != nullptr);
+                    s.attn.n_ctx, cached ? (per_head ? "cached" : "cached-split") : (per_head ? "fused" : "split"), s.attn.mask != nullptr, s.attn.freq_factors != nullptr);
         } else {
             fprintf(stderr, "  [%d] %s '%s'\n", s.node, ggml_op_name(ggml_graph_node(g, s.node)->op), ggml_graph_node(g, s.node)->name);
         }

@@ -34,9 +34,9 @@
 
 namespace mi355 {
 
-// STEP_ROPE_TAB / STEP_QKV / STEP_ATTN_CACHED: the round-3 form of launches 1 and 2 - one cos / sin table launch per graph, RoPE + KV store in the
-// epilogue of the wq | wk | wv launch, attention over cached cells (pm355_rope_table / pm355_mul_mat_vec_qkv / pm355_attn_cached)
-enum step_kind : int32_t { STEP_NODE = 0, STEP_GEMV = 1, STEP_ATTN = 2, STEP_ATTN_BATCH = 3, STEP_ROPE_TAB = 4, STEP_QKV = 5, STEP_ATTN_CACHED = 6 };
+// STEP_ROPE_TAB / STEP_QKV: the round-3 form of launch 1 - one cos / sin table launch per graph, RoPE + KV store in the epilogue of the
+// wq | wk | wv launch (pm355_rope_table / pm355_mul_mat_vec_qkv); STEP_ATTN then runs a form over cached cells. STEP_ATTN: pm355_attn_token_run
+enum step_kind : int32_t { STEP_NODE = 0, STEP_GEMV = 1, STEP_ATTN = 2, STEP_ATTN_BATCH = 3, STEP_ROPE_TAB = 4, STEP_QKV = 5 };
 
 struct tensor_fp {                                   // everything a node-equivalent kernel reads from a tensor
     const void * data; int32_t type; int32_t pad_; int64_t ne[4]; size_t nb[4];
@@ -53,8 +53,8 @@ struct step {
     // producer-side sum of squares (pm355_mul_mat_vec_fused_ss): ss_out - this single-job launch leaves its per-workgroup partials there;
     // ss_in / n_ss - the rms_norm of this launch (STEP_GEMV or STEP_QKV with norm_w) adds the n_ss partials the step right before it left
     double * ss_out; const double * ss_in; int32_t n_ss; int32_t pad_ss_;
-    // STEP_ATTN (STEP_ATTN_CACHED: the same arguments, q = rotated rows; STEP_ROPE_TAB: rope, attn.d_pos, attn.freq_factors, qs.rope_table)
-    pm355_attn_token_args attn; pm355_rope_params rope;
+    // STEP_ATTN: the form pm355_attn_token_plan chose (PM355_ATTN_FORM_*) and its arguments (STEP_ROPE_TAB: rope, attn.d_pos, attn.freq_factors, qs.rope_table)
+    pm355_attn_token_args attn; pm355_rope_params rope; int32_t attn_form;
     // STEP_QKV (with the STEP_GEMV fields)
     pm355_qkv_store qs;
     // STEP_ATTN_BATCH (multi-token): pm355_attn_prefill_masked
@@ -452,44 +452,37 @@ private:
         }
         const int hi = i;
         const int out_idx = hi - 1;                                  // the CONT node / the RESHAPE of the flash-attention result
-        // supported by the kernels?
-        const bool q8 = kq8 || vq8;                                   // quantized cache: one workgroup per head only, head_dim 64 / 128
-        // long contexts: keys split over workgroups; a quantized cache takes the matrix-core kernel over cached cells behind a rope + store launch (round 5)
-        const bool can_split = (dh == 64 || dh == 128) && H / Hkv <= 8 &&
-                               (!q8 || (fa && c_.attn_mfma && pm355_attn_cached_long_check((int) H, (int) Hkv, (int) dh, (int) n_ctx) == 0));
-        const bool can_fused = dh == 64 || dh == 128 || (dh == 256 && !q8);
-        bool split = n_kv >= c_.split_min && can_split;
-        float * split_mem = nullptr;
-        if (split) {
-            split_mem = c_.split_scratch ? c_.split_scratch(c_.user, pm355_attn_split_scratch_floats((int) H, (int) dh, (int) n_ctx)) : nullptr;
-            if (!split_mem) split = false;
-        }
-        // one workgroup per head: the score buffer lives in LDS, sized for split_min (+ one padding step of the cache) or, when the
-        // split kernels cannot serve this shape, for the whole cache
-        const int64_t max_keys = can_split ? c_.split_min + 32 : (q8 && n_ctx > 32768 ? 32768 : n_ctx);
-        if (!split && !(can_fused && n_kv <= max_keys && (size_t) (4 * dh + (fa ? 2048 : 256) + max_keys + 16) * 4 <= 150 * 1024)) return 0;
+        // launch 1: norm + QKV
         float * sq = c_.qkv_scratch ? c_.qkv_scratch(c_.user, (size_t) Eq, (size_t) Ekv) : nullptr;
         if (!sq) return 0;
         float * sk = sq + Eq, * sv = sk + Ekv;
+        pm355_matvec_job jobs[3] = { job_of(mq, sq, bq, nullptr), job_of(mk, sk, bk, nullptr), job_of(mv, sv, bv, nullptr) };
+        const bool one_launch = pm355_mul_mat_vec_fused_check(jobs, 3, E) == 0;
+        if (!one_launch) for (int j = 0; j < 3; ++j) if (pm355_mul_mat_vec_fused_check(jobs + j, 1, E)) return 0;
+        // launch 2: the library says which attention form serves the layer (pm355_attn_token_plan). The round-3 form - RoPE + KV store in the epilogue of
+        // ONE wq | wk | wv launch, attention over cached cells - is this side's to offer: every workgroup's row slices hold whole rotation pairs, and the
+        // cos / sin table is the one of the layers planned before (same parameters, positions and frequency factors)
+        pm355_rope_params rp_; rope_params_of(rq, rp_);
+        const float * ff_ = rq->src[2] ? (const float *) rq->src[2]->data : nullptr;
+        const int32_t flags = (fa ? (PM355_ATTN_V_ROWMAJOR | PM355_ATTN_MASK_F16) : 0) | (kq8 ? PM355_ATTN_K_Q8_0 : 0) | (vq8 ? PM355_ATTN_V_Q8_0 : 0);
+        pm355_attn_plan_in pin = { (int32_t) H, (int32_t) Hkv, (int32_t) dh, (int32_t) n_ctx, (int32_t) n_kv, flags, c_.split_min, c_.attn_mfma, 0, rp_.mode, rp_.n_dims,
+                                   c_.split_scratch != nullptr, 0 };
+        pin.rotated_q = c_.rope_tab && one_launch && pm355_mul_mat_vec_qkv_check_ex(jobs, E, (int) Hkv, (int) dh, rp_.n_dims, rp_.mode & 2) == 0;
+        pm355_attn_plan_out po;
+        pm355_attn_token_plan(&pin, &po);
+        if (po.rotated_q && tab_set_) {
+            const bool same_ff = ff_ == tab_ff_ || (ff_ && tab_ff_ && c_.same_bytes && c_.same_bytes(c_.user, ff_, tab_ff_, (size_t) rp_.n_dims / 2 * 4));
+            if (memcmp(&rp_, &tab_rp_, sizeof(rp_)) || rq->src[1]->data != tab_pos_ || !same_ff) { pin.rotated_q = 0; pm355_attn_token_plan(&pin, &po); }
+        }
+        float * split_mem = po.scratch_floats ? c_.split_scratch(c_.user, (size_t) po.scratch_floats) : nullptr;
+        if (po.scratch_floats && !split_mem) { pin.scratch = 0; pm355_attn_token_plan(&pin, &po); }      // no memory: what serves the layer without
+        if (po.form == PM355_ATTN_FORM_NONE) return 0;
+        const bool epi = po.rotated_q;
         // one cell / cells-attended pair per graph
         if (p.has_attn && (cell_ != cell || n_kv_ != n_kv)) return 0;
         const int outs[2] = {out_idx, mask_cast};
         if (!range_private(i0, hi, outs, mask_cast >= 0 ? 2 : 1)) return 0;
         if (mask_cast >= 0) emit_node(p, mask_cast);                 // the F16 mask is produced first: later layers' graphs-in-graph read it too
-        // launch 1: norm + QKV
-        pm355_matvec_job jobs[3] = { job_of(mq, sq, bq, nullptr), job_of(mk, sk, bk, nullptr), job_of(mv, sv, bv, nullptr) };
-        const bool one_launch = pm355_mul_mat_vec_fused_check(jobs, 3, E) == 0;
-        if (!one_launch) for (int j = 0; j < 3; ++j) if (pm355_mul_mat_vec_fused_check(jobs + j, 1, E)) return 0;
-        // round-3 form: NORM-mode rope, F16 caches, one-workgroup-per-head regime, every workgroup's row slices hold whole rotation pairs, and
-        // the same cos / sin table as the layers planned before (same parameters, positions and frequency factors)
-        pm355_rope_params rp_; rope_params_of(rq, rp_);
-        const float * ff_ = rq->src[2] ? (const float *) rq->src[2]->data : nullptr;
-        bool epi = c_.rope_tab && one_launch && !q8 && (!split || (c_.attn_mfma && pm355_attn_cached_long_check((int) H, (int) Hkv, (int) dh, (int) n_ctx) == 0)) && (rp_.mode == 0 || rp_.mode == 2) && rp_.n_dims <= 256 &&
-                   pm355_mul_mat_vec_qkv_check_ex(jobs, E, (int) Hkv, (int) dh, rp_.n_dims, rp_.mode & 2) == 0;
-        if (epi && tab_set_) {
-            const bool same_ff = ff_ == tab_ff_ || (ff_ && tab_ff_ && c_.same_bytes && c_.same_bytes(c_.user, ff_, tab_ff_, (size_t) rp_.n_dims / 2 * 4));
-            if (memcmp(&rp_, &tab_rp_, sizeof(rp_)) || rq->src[1]->data != tab_pos_ || !same_ff) epi = false;
-        }
         if (epi && !tab_set_) {
             step t; memset(&t, 0, sizeof(t));
             t.kind = STEP_ROPE_TAB; t.node = -1; t.node_lo = i0; t.node_hi = i0;
@@ -508,20 +501,17 @@ private:
             ++p.n_gemv;
         } else if (one_launch) push_gemv(p, i0, hi, jobs, 3, E, (const float *) x->data, nw, eps);
         else for (int j = 0; j < 3; ++j) push_gemv(p, i0, hi, jobs + j, 1, E, (const float *) x->data, nw, eps);
-        // launch 2: rope + KV store + attention (round-3 form: attention over cached cells)
+        // launch 2: the planned form (raw projections: rope + KV store + attention; rotated rows: attention over cached cells, no position to read)
         step s; memset(&s, 0, sizeof(s));
-        s.kind = epi ? STEP_ATTN_CACHED : STEP_ATTN; s.node = -1; s.node_lo = i0; s.node_hi = hi;
+        s.kind = STEP_ATTN; s.attn_form = po.form; s.node = -1; s.node_lo = i0; s.node_hi = hi;
         s.attn.q = sq; s.attn.k = sk; s.attn.v = sv; s.attn.k_cache = kcache->data; s.attn.v_cache = vcache->data;
-        s.attn.d_pos = (const int32_t *) rq->src[1]->data; s.attn.d_cell_nkv = c_.d_dyn;
+        s.attn.d_pos = epi ? nullptr : (const int32_t *) rq->src[1]->data; s.attn.d_cell_nkv = c_.d_dyn;
         s.attn.mask = mask ? mask->data : nullptr;
-        s.attn.flags = (fa ? (PM355_ATTN_V_ROWMAJOR | PM355_ATTN_MASK_F16) : 0) | (kq8 ? PM355_ATTN_K_Q8_0 : 0) | (vq8 ? PM355_ATTN_V_Q8_0 : 0);
-        s.attn.freq_factors = rq->src[2] ? (const float *) rq->src[2]->data : nullptr;
-        s.attn.out = (float *) out_t->data; s.attn.scratch = split ? split_mem : nullptr;
+        s.attn.flags = flags;
+        s.attn.freq_factors = ff_;
+        s.attn.out = (float *) out_t->data; s.attn.scratch = split_mem;
         s.attn.n_head = (int32_t) H; s.attn.n_head_kv = (int32_t) Hkv; s.attn.head_dim = (int32_t) dh; s.attn.n_ctx = (int32_t) n_ctx;
-        int64_t grid_cells = 1024;                                    // long-context grid: power-of-two bucket of the cells attended, so that the plan
-        while (grid_cells < n_kv) grid_cells *= 2;                    // (and its captured hipGraph) survives the steps of n_kv inside a bucket
-        if (grid_cells > n_ctx) grid_cells = n_ctx;
-        s.attn.split = split ? 1 : 0; s.attn.max_keys = split ? (int32_t) grid_cells : (int32_t) max_keys; s.attn.kq_scale = scale;
+        s.attn.max_keys = po.cells; s.attn.kq_scale = scale;
         rope_params_of(rq, s.rope);
         p.steps.push_back(s);
         ++p.n_attn;

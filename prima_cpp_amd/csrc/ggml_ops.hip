@@ -417,9 +417,8 @@ int pm355_op_flash_attn_ext(const pm355_tensor * q, const pm355_tensor * k, cons
     if (q->ne[2] % k->ne[2] || q->ne[2] % v->ne[2] || q->ne[3] % k->ne[3] || q->ne[3] % v->ne[3]) return PM355_E_SHAPE;
     if (mask && (mask->type != PM_F16 || mask->ne[0] != k->ne[1] || mask->ne[1] < q->ne[1] || mask->nb[0] != 2)) return PM355_E_UNSUPPORTED;
     if (dst->ne[0] != q->ne[0] || dst->ne[1] != q->ne[2] || dst->ne[2] != q->ne[1]) return PM355_E_SHAPE;
-    const int Dp = ((int) q->ne[0] + 7) & ~7, nslot = 256 / (Dp / 8);
-    const size_t lds = ((size_t) Dp + (((size_t) k->ne[1] + 3) & ~(size_t) 3) + (size_t) nslot * Dp) * 4;
-    if (lds > 150 * 1024) return PM355_E_RANGE;
+    const size_t lds = pm_flash_attn_ext_lds(q->ne[0], k->ne[1]);
+    if (lds > PM_ATTN_LDS_MAX) return PM355_E_RANGE;
     if (logit_softcap != 0.0f) scale /= logit_softcap;
     const unsigned n_head = (unsigned) q->ne[2];
     const unsigned n_head_log2 = 1u << (unsigned) floor(log2((double) n_head));

@@ -343,11 +343,11 @@ int pm_launch_attn_decode(const pm_attn_tok & a, hipStream_t st) {
     return 0;
 }
 
+bool pm_attn_rope_fused_ok(const pm_attn_tok & t) { return pm_attn_head_shape_ok(t) && t.rope && !t.k_q8 && !t.v_q8 && t.n_tok == 1; }
 int pm_launch_attn_rope_fused(const pm_attn_tok & t, hipStream_t st) {
+    if (!pm_attn_rope_fused_ok(t)) return -1;
     const int dh = t.dh;
-    if ((dh != 64 && dh != 128 && dh != 256) || t.n_ctx % 8) return -1;
     const size_t lds = pm_attn_head_lds(dh, t.n_ctx, t.v_rowmajor, t.cells);
-    if (lds > PM_ATTN_LDS_MAX || !t.rope || t.k_q8 || t.v_q8 || t.n_tok != 1) return -1;
     auto launch = [&](auto kern) {
         pm_allow_big_lds((const void *) kern, lds);
         AttnP a = {t.q, t.k, t.v, (uint16_t *) t.kc, (uint16_t *) t.vc, t.pos, t.seq, t.seq_stride, t.freq_factors, t.out, t.H, t.Hkv, t.n_ctx, t.scale,

@@ -46,19 +46,30 @@ struct pm_attn_tok {
     int cells;                             // > 0: keys the LDS score buffer (per-head forms) / the grid (flash forms) is sized for; the caller guarantees cells attended <= cells
     int n_tok = 1;                         // decode and cached forms, engine mode: token t attends cells [0, pos + t], q / out rows t
 };
-// dynamic LDS bytes of the per-head kernels (rope_fused, cached); beyond PM_ATTN_LDS_MAX the launchers refuse.
-// ggml_graph_plan.h keeps a bound of its own (the plug-in links only the C ABI): it must stay at least as strict as this one.
+// Every form has its predicate next to its launcher: what pm_X_ok(a) accepts pm_launch_X(a) launches, and the launcher refuses (-1) exactly what
+// the predicate refuses. pm_attn_token_plan (attn_plan.hip) chooses among the forms with the same predicates.
+// dynamic LDS bytes of the per-head kernels (rope_fused, cached); beyond PM_ATTN_LDS_MAX the launchers refuse
 constexpr size_t PM_ATTN_LDS_MAX = 150 * 1024;
 inline size_t pm_attn_head_lds(int dh, int n_ctx, bool v_rowmajor, int cells) {
     return (size_t) (4 * dh + (v_rowmajor ? 2048 : 256) + (cells > 0 ? ((cells + 7) & ~7) : n_ctx) + 8) * 4;
 }
+inline bool pm_attn_head_shape_ok(const pm_attn_tok & a) {          // head_dim list and score buffer of the two per-head kernels
+    return (a.dh == 64 || a.dh == 128 || a.dh == 256) && a.n_ctx % 8 == 0 && pm_attn_head_lds(a.dh, a.n_ctx, a.v_rowmajor, a.cells) <= PM_ATTN_LDS_MAX;
+}
 int  pm_launch_attn_decode(const pm_attn_tok & a, hipStream_t st);       // cached cells, scores in LDS sized for n_ctx, q rounded to F16 by the kernel (layer_ops.hip)
+bool pm_attn_rope_fused_ok(const pm_attn_tok & a);
 int  pm_launch_attn_rope_fused(const pm_attn_tok & a, hipStream_t st);   // raw projections: RoPE + KV store + attention, one workgroup per head (layer_ops.hip)
 // decode path with the RoPE + KV-store epilogue in the wq | wk | wv launch (mmvq_device.h QkvEpi): q = rotated, F16-rounded rows (attn_cached.hip)
+bool pm_attn_cached_ok(const pm_attn_tok & a);
 int  pm_launch_attn_cached(const pm_attn_tok & a, hipStream_t st);
-// long context, keys split over workgroups, three launches (attn_split.hip). rope == null: q = ROTATED queries and the caches are already
+// long context over raw projections or rotated rows, keys split over workgroups (attn_split.hip, attn_flash.hip): a workgroup serves the whole group
+// of query heads of its KV head, at most PM_ATTN_GROUP_MAX of them (RMAX of both files); head_dim 64 / 128
+constexpr int PM_ATTN_GROUP_MAX = 8;
+inline bool pm_attn_split_heads_ok(int H, int Hkv, int dh) { return (dh == 64 || dh == 128) && Hkv >= 1 && H % Hkv == 0 && H / Hkv <= PM_ATTN_GROUP_MAX; }
+// three launches (attn_split.hip). rope == null: q = ROTATED queries and the caches are already
 // updated; else q / k / v are the raw projections and rope + KV store happen inside the first kernel
 size_t pm_attn_split_scratch_floats(int H, int dh, int n_ctx);
+bool pm_attn_split_ok(const pm_attn_tok & a);
 int  pm_launch_attn_split(const pm_attn_tok & a, hipStream_t st);
 // The scratch of the two one-launch long-context forms and of the Q8_0 path in front of the second, in floats.
 // Both kernels may run on one scratch in one process: each has ticket words of its own
@@ -85,9 +96,11 @@ inline size_t pm_attn_long_scratch_floats(int H, int Hkv, int dh, int n_ctx) {
     return std::max(pm_attn_split_scratch_floats(H, dh, n_ctx), pm_attn_flash_layout(H, Hkv, dh, n_ctx).total);
 }
 // long context in ONE launch (flash-decoding with an in-launch merge, attn_flash.hip); q / k / v raw projections
+bool pm_attn_flash_ok(const pm_attn_tok & a);
 int  pm_launch_attn_flash(const pm_attn_tok & a, hipStream_t st);
-// long context over cached cells on the matrix cores (attn_flash_mfma.hip); F16 or Q8_0 caches
-int  pm_attn_flash_cached_ok(int H, int Hkv, int dh, int n_ctx);      // 0: served by the matrix-core long-context kernel
+// long context over cached cells on the matrix cores (attn_flash_mfma.hip); F16 or Q8_0 caches. The shape rule reads the CU count: n_cus <= 0 = the device's
+bool pm_attn_flash_cached_shape_ok(int H, int Hkv, int dh, int n_ctx, int n_cus = 0);
+bool pm_attn_flash_cached_ok(const pm_attn_tok & a, int n_cus = 0);
 int  pm_launch_attn_flash_cached(const pm_attn_tok & a, hipStream_t st);
 // ---- multi-token attention over cached cells on MFMA (attn_prefill.hip) -----------------------------------------------------------------------
 // q = rotated query rows [n_tok][H * dh], the caches already hold the tokens. Engine mode (pos): token t attends cells [0, pos[seq ? *seq : 0] + t], causal.
@@ -102,17 +115,33 @@ struct pm_attn_batch {
 };
 int  pm_launch_attn_prefill(const pm_attn_batch & a, hipStream_t st);
 // the per-token cos / sin table the QKV epilogue reads (tab[2 i], tab[2 i + 1] for rotation pair i; position = pos[seq ? *seq : 0])
+constexpr int PM_ROPE_TABLE_DIMS_MAX = 256;          // n_dims the table (and the buffers its callers keep for it) holds
 void pm_launch_rope_table(const pm_rope_cfg & c, const int32_t * pos, const int32_t * seq, const float * freq_factors, float * tab, hipStream_t st,
                           int n_tok = 1);    // n_tok > 1: tables of the tokens pos .. pos + n_tok - 1, n_dims floats each
 void pm_launch_set_i32x2(int32_t * p, int a, int b, hipStream_t st);
+// dynamic LDS bytes of the two FLASH_ATTN_EXT node kernels (ggml_ops.hip; Q8_0 K / V: attn_q8.hip): the padded query row, one query's scores, the slots' partial rows
+inline size_t pm_flash_attn_ext_lds(int64_t head_dim, int64_t n_kv) {
+    const size_t Dp = ((size_t) head_dim + 7) & ~(size_t) 7;
+    return (Dp + (((size_t) n_kv + 3) & ~(size_t) 3) + 256 / (Dp / 8) * Dp) * 4;
+}
 // quantized (Q8_0) KV cache, native 34-byte blocks (attn_q8.hip)
 int  pm_launch_cpy_f32_q8_0(const pm355_tensor * src, void * dst, hipStream_t st);
 int  pm_launch_flash_attn_ext_q8(const pm355_tensor * q, const pm355_tensor * k, const pm355_tensor * v, const pm355_tensor * mask,
                                  const pm355_tensor * dst, float scale, float softcap, hipStream_t st);
 // Q8_0 caches (row-major V), ggml-graph mode, raw projections. prep: RoPE + quantizing KV store, a.out receives the operand rows of the K.q product
 // (then pm_launch_attn_flash_cached runs over the cached cells); token: the same plus the attention, one workgroup per head
+bool pm_attn_q8_token_prep_ok(const pm_attn_tok & a);
 int  pm_launch_q8_token_prep(const pm_attn_tok & a, hipStream_t st);
+bool pm_attn_q8_token_ok(const pm_attn_tok & a);
 int  pm_launch_attn_q8_token(const pm_attn_tok & a, hipStream_t st);
+constexpr int PM_ATTN_Q8_TOKEN_CELLS_MAX = 32768;      // ggml-graph mode: the per-head Q8_0 kernel's score buffer is never sized for more cells than this
+// ---- ggml-graph mode: which single-token form serves a layer, and the one switch that runs a form (attn_plan.hip) ------------------------------
+// The plan follows no pointer and needs no device. A form it names is accepted by that form's predicate above, so pm_attn_token_run cannot be
+// refused for the shape or mode the plan saw (it still refuses null pointers).
+void pm_attn_token_plan(const pm355_attn_plan_in & in, pm355_attn_plan_out & out);
+int  pm_attn_long_raw_form();                           // PM355_ATTN_FORM_FLASH, or _SPLIT3 with PM355_ATTN_FLASH=0 in the environment (read once)
+// runs `form` (PM355_ATTN_FORM_*) on the C ABI's argument block; 0, or the refusal as a PM355_E_* code with its text in *why
+int  pm_attn_token_run(int form, const pm355_attn_token_args & a, const pm355_rope_params * rp, hipStream_t st, const char ** why);
 void pm_launch_argmax(const float * x, int n, int32_t * idx, float * val, hipStream_t st);
 void pm_launch_add(const float * a, const float * b, float * y, long n, long nb, hipStream_t st);
 void pm_launch_mul(const float * a, const float * b, float * y, long n, long nb, hipStream_t st);

@@ -476,6 +476,50 @@ def attn_token(q, k, v, k_cache, v_cache, pos, cell_nkv, n_head, n_head_kv, head
     return out
 
 
+ATTN_FORM_NONE, ATTN_FORM_ROPE_FUSED, ATTN_FORM_FLASH, ATTN_FORM_SPLIT3, ATTN_FORM_Q8_TOKEN, ATTN_FORM_Q8_LONG, ATTN_FORM_CACHED, ATTN_FORM_CACHED_LONG = range(8)
+
+
+class AttnPlanIn(__import__("ctypes").Structure):
+    import ctypes as _C
+    _i = _C.c_int32
+    _fields_ = [("n_head", _i), ("n_head_kv", _i), ("head_dim", _i), ("n_ctx", _i), ("n_kv", _i), ("flags", _i), ("split_min", _i), ("attn_mfma", _i),
+                ("rotated_q", _i), ("rope_mode", _i), ("rope_n_dims", _i), ("scratch", _i), ("n_cus", _i)]
+
+
+class AttnPlanOut(__import__("ctypes").Structure):
+    import ctypes as _C
+    _fields_ = [("form", _C.c_int32), ("cells", _C.c_int32), ("rotated_q", _C.c_int32), ("pad_", _C.c_int32), ("scratch_floats", _C.c_int64)]
+
+
+def attn_token_plan(n_head, n_head_kv, head_dim, n_ctx, n_kv, flags=0, split_min=320, attn_mfma=True, rotated_q=False, rope_mode=0, rope_n_dims=None,
+                    scratch=True, n_cus=0):
+    """pm355_attn_token_plan: the form (ATTN_FORM_*) that serves one token's attention in ggml-graph mode, with .cells, .scratch_floats, .rotated_q. No device work."""
+    import ctypes as C
+    lib = L.load()
+    lib.pm355_attn_token_plan.restype = C.c_int
+    lib.pm355_attn_token_plan.argtypes = [C.c_void_p, C.c_void_p]
+    i = AttnPlanIn(n_head, n_head_kv, head_dim, n_ctx, n_kv, flags, split_min, int(attn_mfma), int(rotated_q), rope_mode, rope_n_dims or head_dim, int(scratch), n_cus)
+    o = AttnPlanOut()
+    check(lib.pm355_attn_token_plan(C.addressof(i), C.addressof(o)), "attn_token_plan")
+    return o
+
+
+def attn_token_run(form, q, k, v, k_cache, v_cache, pos, cell_nkv, n_head, n_head_kv, head_dim, n_ctx, scale, flags=0, mask=None, freq_factors=None, scratch=None,
+                   max_keys=0, mode=0, freq_base=10000.0, n_dims=None, n_ctx_orig=8192, freq_scale=1.0, ext_factor=0.0, attn_factor=1.0,
+                   beta_fast=32.0, beta_slow=1.0):
+    """pm355_attn_token_run: `form` (what attn_token_plan answered) on attn_token's arguments; the cached forms read q as rotated rows and neither k, v nor pos."""
+    import ctypes as C
+    lib = L.load()
+    lib.pm355_attn_token_run.restype = C.c_int
+    lib.pm355_attn_token_run.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    out = torch.empty(n_head * head_dim, dtype=torch.float32, device=q.device)
+    a = AttnTokenArgs(ptr(q), ptr(k), ptr(v), ptr(k_cache), ptr(v_cache), ptr(pos), ptr(cell_nkv), ptr(mask), ptr(freq_factors), ptr(out), ptr(scratch),
+                      n_head, n_head_kv, head_dim, n_ctx, 0, max_keys, float(scale), flags)
+    rp = RopeParams(n_dims or head_dim, mode, n_ctx_orig, freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow)
+    check(lib.pm355_attn_token_run(form, C.addressof(a), C.addressof(rp), stream_ptr()), "attn_token_run")
+    return out
+
+
 class QkvAttn(__import__("ctypes").Structure):
     import ctypes as _C
     _fields_ = [("out", _C.c_void_p), ("ticket", _C.c_void_p), ("watchdog", _C.c_void_p), ("kq_scale", _C.c_float), ("n_head", _C.c_int32), ("max_keys", _C.c_int32)]

@@ -1,6 +1,8 @@
 """GPU parity tests (run with -m gpu on an MI355X): every op goes through the C ABI of
 libprima_mi355.so and is compared with the CPU oracle on the same seeded inputs.
 Integer / byte results: bit-exact. Float results: tolerance stated per test."""
+import os
+
 import numpy as np
 import pytest
 
@@ -1537,6 +1539,74 @@ def test_attn_token_f16_caches_cell_mask_and_each_layout_flag_alone(P, form, fla
         want = p @ V[:, hk * dh:(hk + 1) * dh].astype(np.float64)
         print(f"{form} flags {flags} head {h}: max |d out| {np.abs(out[h] - want).max():.3g}, max |out| {np.abs(want).max():.3g}")
         assert np.abs(out[h] - want).max() <= 2e-3 * np.abs(want).max() + 1e-4, h
+
+
+# ---- the planned form through pm355_attn_token_run against the entry that used to own that form ------------------------------------------------------
+# The smallest shapes at which pm355_attn_token_plan's choice flips: 24 and 40 cells attended around split_min = 32 (per-head form / long-context form),
+# head_dim 64 / 128 (+ 256, which only the F16 per-head kernels serve), the default and the flash-attention cache layout, Q8_0 K / V alone and together,
+# raw projections and rotated rows. Same inputs, zeroed scratch of the reported size for each side: same bytes out, and in the caches of the forms that store.
+_PLAN_RUN_CASES = [(dh, n_kv, fa, kq8, vq8, rot) for dh in (64, 128) for n_kv in (24, 40)
+                   for fa, kq8, vq8, rot in ((0, 0, 0, 0), (0, 0, 0, 1), (1, 0, 0, 0), (1, 0, 0, 1), (1, 1, 0, 0), (1, 0, 1, 0), (1, 1, 1, 0))] + \
+                  [(256, 24, 0, 0, 0, 0), (256, 24, 0, 0, 0, 1)]
+_plan_run_q8 = {}
+
+
+def _plan_run_q8_rows(oracle, Ekv):
+    """48 cells of native Q8_0 blocks (a cache's other cells stay zero blocks), computed once per row width"""
+    if Ekv not in _plan_run_q8:
+        f = np.random.default_rng(Ekv).normal(0, 1, (48, Ekv)).astype(np.float32)
+        _plan_run_q8[Ekv] = np.concatenate([oracle.quantize_row_q8_0(f[i]) for i in range(48)])
+    return _plan_run_q8[Ekv]
+
+
+@pytest.mark.parametrize("dh,n_kv,fa,kq8,vq8,rot", _PLAN_RUN_CASES)
+def test_planned_attention_form_runs_as_the_entry_that_owned_it(P, oracle, dh, n_kv, fa, kq8, vq8, rot):
+    torch = P.torch
+    H, Hkv, n_ctx, split_min = 4, 2, 1088, 32
+    Ekv, cell = Hkv * dh, n_kv - 1
+    flags = (P.ATTN_V_ROWMAJOR | P.ATTN_MASK_F16 if fa else 0) | (P.ATTN_K_Q8_0 if kq8 else 0) | (P.ATTN_V_Q8_0 if vq8 else 0)
+    plan = P.attn_token_plan(H, Hkv, dh, n_ctx, n_kv, flags=flags, split_min=split_min, attn_mfma=True, rotated_q=bool(rot))
+    long_raw = P.ATTN_FORM_SPLIT3 if os.environ.get("PM355_ATTN_FLASH", "")[:1] == "0" else P.ATTN_FORM_FLASH
+    want_form = ((P.ATTN_FORM_CACHED_LONG if rot else P.ATTN_FORM_Q8_LONG if kq8 or vq8 else long_raw) if n_kv >= split_min and dh != 256 else
+                 (P.ATTN_FORM_CACHED if rot else P.ATTN_FORM_Q8_TOKEN if kq8 or vq8 else P.ATTN_FORM_ROPE_FUSED))
+    long_form = want_form in (P.ATTN_FORM_CACHED_LONG, P.ATTN_FORM_Q8_LONG, long_raw)
+    print(f"dh {dh} n_kv {n_kv} flags {flags} rotated {rot}: form {plan.form}, cells {plan.cells}, scratch floats {plan.scratch_floats}")
+    assert plan.form == want_form and bool(plan.rotated_q) == bool(rot) and (plan.scratch_floats > 0) == long_form
+    assert plan.cells == (1024 if long_form else n_ctx if dh == 256 else split_min + 32)
+    rng = np.random.default_rng(1000 * dh + 10 * n_kv + flags + rot)
+
+    def cache(q8, transposed):
+        if q8:
+            c = torch.zeros(n_ctx * (Ekv // 32 * 34), dtype=torch.uint8, device="cuda")
+            rows = _plan_run_q8_rows(oracle, Ekv)
+            c[:rows.size] = torch.from_numpy(rows).cuda()
+            return c
+        a = np.zeros((n_ctx, Ekv), dtype=np.float16)
+        a[:n_kv] = rng.normal(0, 1, (n_kv, Ekv)).astype(np.float16)
+        return torch.from_numpy(np.ascontiguousarray(a.T) if transposed else a).cuda()
+    kc0, vc0 = cache(kq8, False), cache(vq8, not fa)
+    # rotated rows are F16-rounded by the launch that leaves them; raw projections are not
+    qn = rng.normal(0, 1, (1, H * dh)).astype(np.float32)
+    q = _dev(P, qn.astype(np.float16).astype(np.float32) if rot else qn)
+    k, v = _dev(P, rng.normal(0, 1, (1, Ekv)).astype(np.float32)), _dev(P, rng.normal(0, 1, (1, Ekv)).astype(np.float32))
+    hidden = np.arange(64) % 5 == 2                                   # (the row is as long as the score buffer: cells beyond n_kv are never attended)
+    mask = torch.from_numpy(np.where(hidden, -np.inf, 0.0).astype(np.float16 if fa else np.float32)).cuda()
+    pos = torch.tensor([cell], dtype=torch.int32, device="cuda")
+    dyn = torch.tensor([cell, n_kv], dtype=torch.int32, device="cuda")
+    scale = 1.0 / np.sqrt(dh)
+    scratch = lambda: torch.zeros(plan.scratch_floats, dtype=torch.float32, device="cuda") if plan.scratch_floats else None
+    kc1, vc1, kc2, vc2 = kc0.clone(), vc0.clone(), kc0.clone(), vc0.clone()
+    got = P.attn_token_run(plan.form, q, k, v, kc1, vc1, None if rot else pos, dyn, H, Hkv, dh, n_ctx, scale, flags=flags, mask=mask, scratch=scratch(),
+                           max_keys=plan.cells, freq_base=500000.0)
+    if rot:
+        ref = P.attn_cached(q, kc2, vc2, None, H, Hkv, dh, n_ctx, scale, cell_nkv=dyn, mask=mask, max_keys=plan.cells, flags=flags, scratch=scratch()).reshape(-1)
+    else:
+        ref = P.attn_token(q, k, v, kc2, vc2, pos, dyn, H, Hkv, dh, n_ctx, scale, flags=flags, mask=mask, scratch=scratch(), max_keys=plan.cells, freq_base=500000.0)
+    torch.cuda.synchronize()
+    assert torch.isfinite(got).all() and got.abs().max().item() > 0
+    assert torch.equal(got.view(torch.int32), ref.view(torch.int32))
+    assert torch.equal(kc1, kc2) and torch.equal(vc1, vc2)
+    assert rot or not (torch.equal(kc1, kc0) or torch.equal(vc1, vc0))          # the raw-projection forms stored the token
 
 
 # ---- every kernel form of the single-token mat-vec against the launch that just misses it --------------------------------------------------------
